@@ -1,10 +1,20 @@
 #!/usr/bin/env python3
 """MGMC V-cycle benchmark (BASELINE.json metric): samples/s of the 3D 512^3 shifted-Laplace
-7-level V-cycle, one independent chain per GPU, plus the fine-smoother HBM roofline and the CPU
-oracle baseline.
+7-level V-cycle, one independent chain per GPU, plus the fine-smoother HBM roofline and, with
+--full, the CPU oracle baseline.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps, writes its outputs (--dump-outputs) and prints
+the line; the roofline figures come from the events of those same K steps.  What takes a run of its
+own -- the CPU baseline, minutes at 512^3 -- runs only with --full (`cpu_baseline` is null otherwise).
+--dump-outputs DIR writes what the K timed steps left with rank 0's sampler (float64 .npy):
+  state.npy       (chains per GPU, m): the chain states after the last step (get_state) at m vertices,
+                  all of them or a fixed seeded sample that keeps the file under 48 MB
+  qoi_series.npy  (chains per GPU, <= K): the QoI recorded after every timed step (get_series)
+  qoi_moments.npy (chains, 3): count, mean, M2 of the QoI per chain of every rank (the all-gather)
+The inputs are fixed (f = 0, x0 = 0, Philox key (SEED, chain)), so equal arguments give equal files.
 
 One process per GPU (RANK / LOCAL_RANK / WORLD_SIZE from the environment).  Each rank runs an
 independent chain (Philox key = (seed, chain = rank)).  The device-side collectives (barrier,
@@ -26,7 +36,7 @@ Rank 0 prints ONE JSON line.  Field notes:
                committed profiles/pmc_traffic.json (a stored figure; `traffic_source` names it)
   config.collectives / rccl_ranks = what the final all-gather ran on and how many ranks the RCCL
                communicator spans (ncclCommCount); a failed communicator exits non-zero
-  cpu_baseline = the CPU oracle (oracle/refcpu.cpp, FAITHFUL mode = the reference algorithm,
+  cpu_baseline = (--full) the CPU oracle (oracle/refcpu.cpp, FAITHFUL mode = the reference algorithm,
                g++ -O3) run as a child process (oracle/baseline.py) on rank 0 at N=1: 1 core
                (3 warm-up + 5 timed cycles) and the all-cores aggregate
 """
@@ -64,6 +74,12 @@ def parse():
     ap.add_argument("--cpu-samples", type=int, default=5, help="V-cycles timed for the 1-core CPU baseline (0 = skip)")
     ap.add_argument("--cpu-warmup", type=int, default=3, help="untimed V-cycles before them")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline (a child process, "
+                         "minutes at 512^3; --cpu-samples / --cpu-warmup / --no-cpu-baseline shape it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write rank 0's state.npy, qoi_series.npy and qoi_moments.npy "
+                         "(float64) into DIR")
     ap.add_argument("--traffic-file", default=os.path.join(ROOT, "profiles", "pmc_traffic.json"))
     ap.add_argument("--plain", action="store_true", help="time the single-graph loop instead of the segmented one")
     ap.add_argument("--timing-stride", type=int, default=0,
@@ -237,6 +253,30 @@ def sweep_roofline(ms, nsweeps, bytes_sweep, traffic, provenance, kernel):
             "kernel": kernel, "bytes_per_launch": bytes_sweep, "avg_launch_ms": round(t * 1e3, 4)}
 
 
+DUMP_STATE_VALUES = 6 * 2 ** 20   # doubles of state.npy over all chains (48 MB)
+DUMP_SERIES_VALUES = 2 ** 20      # doubles of qoi_series.npy over all chains (8 MB)
+
+
+def dump_outputs(path, sampler, steps, moments):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as float64 .npy
+    files (the module docstring lists them), 64 MB at the most.  A state longer than its share is
+    sampled at fixed vertices (default_rng(SEED), ascending), the same for every chain and run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    K, ndof = sampler.nchains, sampler.ndof
+    keep = DUMP_STATE_VALUES // K
+    idx = None if ndof <= keep else np.sort(np.random.default_rng(SEED).integers(0, ndof, keep))
+    state = np.empty((K, ndof if idx is None else keep))
+    for c in range(K):  # one chain on the host at a time (1 GB at 512^3)
+        x = sampler.get_state(c)
+        state[c] = x if idx is None else x[idx]
+    m = min(steps, DUMP_SERIES_VALUES // K)  # the last m timed steps
+    series = np.stack([sampler.get_series(steps, c)[steps - m:] for c in range(K)])
+    np.save(os.path.join(path, "state.npy"), state)
+    np.save(os.path.join(path, "qoi_series.npy"), series)
+    np.save(os.path.join(path, "qoi_moments.npy"), np.asarray(moments, dtype=np.float64).reshape(-1, 3))
+
+
 def main():
     args = parse()
     rank = int(os.environ.get("RANK", "0"))
@@ -303,6 +343,8 @@ def main():
     from multigridmc_amd.distributed import merge_moments
     parts = coll.allgather_moments()
     nq, mean, m2 = merge_moments([tuple(r) for r in parts])
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, sampler, args.steps, parts)
 
     if rank == 0:
         value = world * K * args.steps / elapsed
@@ -332,7 +374,7 @@ def main():
                 for r in (roof, pre):
                     r["kernel"] += " + low-rank noise patch and B_bar fix (same segment)"
         cpu = None
-        if world == 1 and not args.no_cpu_baseline and args.cpu_samples > 0 and not args.fem:
+        if args.full and world == 1 and not args.no_cpu_baseline and args.cpu_samples > 0 and not args.fem:
             pa = None
             if args.posterior:
                 pa = ["--posterior", str(args.posterior), "--radius", str(args.radius)]

@@ -6,7 +6,7 @@ columns).  One JSON object per line into the file given as argv[1]:
             and inputs, 1,000 warm-up + 10,000 samples each (driver_mgmc.cc:40-107), timed; QoI
             mean / variance of both and the exact observed mean / variance
             (linear_operator.hh:153-174);
-  configs 2, 3, 5 (and 4 with --with-512): bench.py lines, CPU baselines included.
+  configs 2, 3, 5 (and 4 with --with-512): bench.py --full lines, CPU baselines included.
 
   python scripts/config_table.py out.jsonl [--with-512]
 """
@@ -69,8 +69,8 @@ def config1():
 
 
 def bench(config, args):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True,
-                       timeout=1800)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + args, capture_output=True,
+                       text=True, timeout=1800)
     if r.returncode != 0:
         raise RuntimeError(r.stderr[-1000:])
     line = json.loads(r.stdout.strip().splitlines()[-1])

@@ -4,7 +4,7 @@
 cd $GRAFT_REPO_ROOT && export TMPDIR=/tmp && O=gpurun_out/${TAG:-r6final} && mkdir -p $O
 python -c "import os; print('affinity', len(os.sched_getaffinity(0)), 'cpu_count', os.cpu_count(), 'OMP', os.environ.get('OMP_NUM_THREADS'))" > $O/cpu.txt
 if [ -z "$SKIP_BENCH" ]; then
-  timeout -k 10 600 python bench.py > $O/bench.log 2>&1; rc=$?
+  timeout -k 10 600 python bench.py --full > $O/bench.log 2>&1; rc=$?
   echo "bench rc=$rc"; tail -1 $O/bench.log | cut -c1-300; [ $rc -eq 0 ] || exit $rc
 fi
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline > $O/prof.log 2>&1; rc=$?

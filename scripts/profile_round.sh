@@ -22,7 +22,7 @@ if [ -n "$RUN_POISON" ]; then
   [ $rc -eq 0 ] || exit $rc
 fi
 if [ -z "$SKIP_BENCH" ]; then
-  timeout -k 10 900 python bench.py ${BENCH_ARGS} > $O/bench.log 2>&1; rc=$?
+  timeout -k 10 900 python bench.py --full ${BENCH_ARGS} > $O/bench.log 2>&1; rc=$?
   echo "bench rc=$rc"; tail -2 $O/bench.log
   [ $rc -eq 0 ] || exit $rc
 fi
