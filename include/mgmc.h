@@ -212,9 +212,14 @@ int mgmc_nchains(const mgmc_handle* h);
 int mgmc_destroy(mgmc_handle* h);
 int mgmc_level_desc_get(const mgmc_handle* h, int level, mgmc_level_desc* out);
 /* The kernels this handle runs on a level (ABI 5), as text "sweep=<kernel>[;post_sweep=<kernel>]
- * [;residual_restrict=<kernel>][;noise=<source>][;lowrank=<path>]" -- for labels (bench.py) and profiles;
+ * [;noise=<source>][;residual_restrict=<kernel>][;rhs=zero][;lowrank=<path>]", the keys in this order -- for
+ * labels (bench.py) and profiles;
  * <source>: restriction | tail | restriction+tail -- sweeps of the level read Box-Muller pairs drawn by the
  * restriction launch before the first pre-sweep and / or a tail launch's spare workgroups;
+ * rhs=zero, on level 0 only: the level's right-hand side is all +0.0 (prior sampling: as created, or after a
+ * mgmc_set_rhs / mgmc_apply of zeros; -0.0, denormals and NaN are not zero) and the cycle's z-marching
+ * sweeps and residual + restriction named above run their instances that take it as a constant instead of
+ * reading it -- same bits; absent on every other level, with a low-rank part, and on the general kernels;
  * <path> on a posterior level: small | rows | dense | dense,rhs_inplace */
 int mgmc_level_kernels(const mgmc_handle* h, int level, char* out, size_t n);
 

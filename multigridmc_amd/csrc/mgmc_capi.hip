@@ -145,8 +145,9 @@ void launch_sweep(const Level& lv, double* x, const double* f, const GibbsArg& g
 #undef DISPATCH
 }
 
+// fz: the right-hand side is known to be all +0.0 (Op::fzero): the FZ instances, which do not load it
 template <int XP, int TY, int NT, int MINW = 1>
-void launch_zsweep_t(const Level& lv, ZSweepArgs a, bool prolong, hipStream_t s, int nch) {
+void launch_zsweep_t(const Level& lv, ZSweepArgs a, bool prolong, hipStream_t s, int nch, bool fz) {
     a.ntx = (lv.L.nx / 2) / XP;
     a.nty = (lv.L.ny - 1 + TY - 1) / TY;
     a.ntz = (lv.L.nz - 1 + a.tz - 1) / a.tz;
@@ -159,6 +160,15 @@ void launch_zsweep_t(const Level& lv, ZSweepArgs a, bool prolong, hipStream_t s,
     const bool pow2 = std::isnormal(a.alpha) && std::frexp(std::fabs(a.alpha), &ex) == 0.5 && ex > -900 && ex < 900;
     const dim3 grid(nb, 1, nch);  // batched chains: blockIdx.z
     const bool lrf = a.lr.e != nullptr;  // the right-hand side read in place (LRRhsArg)
+    if (fz && !lrf) {
+        if (prolong && pow2)
+            hipLaunchKernelGGL((k_zsweep_rb7<XP, TY, NT, 2, MINW, false, true>), grid, dim3(NT), lds, s, a);
+        else if (prolong)
+            hipLaunchKernelGGL((k_zsweep_rb7<XP, TY, NT, 1, MINW, false, true>), grid, dim3(NT), lds, s, a);
+        else
+            hipLaunchKernelGGL((k_zsweep_rb7<XP, TY, NT, 0, MINW, false, true>), grid, dim3(NT), lds, s, a);
+        return;
+    }
     if (prolong && pow2 && lrf)
         hipLaunchKernelGGL((k_zsweep_rb7<XP, TY, NT, 2, MINW, true>), grid, dim3(NT), lds, s, a);
     else if (prolong && pow2)
@@ -198,9 +208,10 @@ static int zsweep_plain_rows(const Level& lv, int nch) {
 }
 
 // lr (non-null): the right-hand side is read in place (LRRhsArg, LowRankDev::rhs_inplace)
+// fzero: f is known to be all +0.0 (the cycle's ops on level 0, Op::fzero): it is not read
 void launch_zsweep(const Level& lv, const double* xin, double* xout, const double* f, const GibbsArg& g0,
                    int direction, const Level* coarse, const double* xc, double alpha, hipStream_t s, int nch = 1,
-                   const LRRhsArg* lr = nullptr) {
+                   const LRRhsArg* lr = nullptr, bool fzero = false) {
     ZSweepArgs a;
     a.lr = lr ? *lr : LRRhsArg{nullptr};
     a.cs = lv.L.nstore;
@@ -218,16 +229,16 @@ void launch_zsweep(const Level& lv, const double* xin, double* xout, const doubl
     a.zpairs = 0;
     if (coarse) {  // fused-prolongation sweep
         a.tz = zsweep_depth(lv, ZS_TYP, ZS_TZP);
-        launch_zsweep_t<ZS_XP, ZS_TYP, ZS_NTP, ZS_MINWP>(lv, a, true, s, nch);
+        launch_zsweep_t<ZS_XP, ZS_TYP, ZS_NTP, ZS_MINWP>(lv, a, true, s, nch, fzero);
         return;
     }
     a.tz = zsweep_depth(lv, ZS_TY, ZS_TZ);
     a.zpairs = 1;  // z-chunks in up / down pairs (mgmc_zsweep.hpp)
     if (zsweep_plain_rows(lv, nch) != ZS_TY) {
-        launch_zsweep_t<ZS_XP, ZS_TYP, ZS_NTP, ZS_MINWP>(lv, a, false, s, nch);
+        launch_zsweep_t<ZS_XP, ZS_TYP, ZS_NTP, ZS_MINWP>(lv, a, false, s, nch, fzero);
         return;
     }
-    launch_zsweep_t<ZS_XP, ZS_TY, ZS_NT, ZS_MINW>(lv, a, false, s, nch);
+    launch_zsweep_t<ZS_XP, ZS_TY, ZS_NT, ZS_MINW>(lv, a, false, s, nch, fzero);
 }
 
 // colour-pair passes of a Galerkin 9/27-point level (in place): forward colours (0,1), (2,3), ...,
@@ -481,7 +492,7 @@ void launch_coarse_lds(const Level& lv, const GibbsArg& g, int nsweeps, hipStrea
 }
 
 
-template <int NPTS, int CX, int CY, int NT, bool SYM = false, bool LRF = false>
+template <int NPTS, int CX, int CY, int NT, bool SYM = false, bool LRF = false, bool FZ = false>
 void launch_zresrestrict_t(const Level& lf, const Level& lc, const double* x, const double* f, double* fc, double* xc,
                            hipStream_t s, int nch, const TailNoiseLaunch* tn = nullptr, const LRRhsArg* lr = nullptr,
                            const PreNoiseLaunch* pn = nullptr) {
@@ -541,7 +552,7 @@ void launch_zresrestrict_t(const Level& lf, const Level& lc, const double* x, co
     a.ntz = (lc.L.nz - 1 + a.kz - 1) / a.kz;
     const int nt = a.ntx * a.nty * a.ntz;
     const int nb = (nt + 7) / 8 * 8;
-    if (tn && !LRF) {
+    if (tn && !LRF && !FZ) {
         a.nblk_main = nb;
         a.jobs = tn->jobs;
         a.njobs = tn->njobs;
@@ -556,7 +567,7 @@ void launch_zresrestrict_t(const Level& lf, const Level& lc, const double* x, co
                            zrestrict_lds_bytes(CX, CY), s, a);
         return;
     }
-    hipLaunchKernelGGL((k_zresrestrict<NPTS, CX, CY, NT, false, SYM, LRF>), dim3(nb, 1, nch), dim3(NT),
+    hipLaunchKernelGGL((k_zresrestrict<NPTS, CX, CY, NT, false, SYM, LRF, FZ>), dim3(nb, 1, nch), dim3(NT),
                        zrestrict_lds_bytes(CX, CY), s, a);
 }
 
@@ -580,7 +591,7 @@ bool zres_draws_noise(const Level& lf, const Level& lc) {
 
 void launch_residual_restrict(const Level& lf, const Level& lc, const double* x, const double* f, double* fc,
                               double* xc, int zero_xc, hipStream_t s, int nch, const TailNoiseLaunch* tn,
-                              bool skip_xc, const LRRhsArg* lr, const PreNoiseLaunch* pn) {
+                              bool skip_xc, const LRRhsArg* lr, const PreNoiseLaunch* pn, bool fzero) {
     const bool zr = lf.spec.dim == 3 && zero_xc && !lf.field && !(lf.paths & PATH_NO_ZRESTRICT) && lc.L.nx >= 8;
     if (nch > 1 && !zr) {  // batched chains on the generic kernels: one launch per chain
         for (int c = 0; c < nch; ++c)
@@ -612,6 +623,11 @@ void launch_residual_restrict(const Level& lf, const Level& lc, const double* x,
             if ((long long)((lc.L.nx + 62) / 64) * ((lc.L.ny + 6) / 8) * (lc.L.nz - 1) >= tune::ZR7_WIDE_MIN_TILES)
                 launch_zresrestrict_t<7, 64, 8, 512, false, true>(lf, lc, x, f, fc, xc, s, nch, nullptr, lr);
             else launch_zresrestrict_t<7, 64, 4, 256, false, true>(lf, lc, x, f, fc, xc, s, nch, nullptr, lr);
+        } else if (lf.spec.npoints == 7 && fzero && !small) {
+            // f known to be all +0.0 (Op::fzero, rhs_zero_residual_ok: never the small kernel): the FZ instances
+            if ((long long)((lc.L.nx + 62) / 64) * ((lc.L.ny + 6) / 8) * (lc.L.nz - 1) >= tune::ZR7_WIDE_MIN_TILES)
+                launch_zresrestrict_t<7, 64, 8, 512, false, false, true>(lf, lc, x, f, fc, xc, s, nch);
+            else launch_zresrestrict_t<7, 64, 4, 256, false, false, true>(lf, lc, x, f, fc, xc, s, nch);
         } else if (lf.spec.npoints == 7) {
             if (small) launch_zresrestrict_t<7, 16, 4, 64>(lf, lc, x, f, fc, xc, s, nch, tn);
             // 64 x 8 coarse points, 512 threads, 80 KB of LDS (2 workgroups per CU): half the y halo
@@ -1574,6 +1590,35 @@ void mark_zero_inputs(mgmc_handle* h) {
     }
 }
 
+// Level 0's right-hand side in prior sampling is f = A 0 = 0 (the reference fixes it once, Sampler::fix_rhs;
+// mgmc_create zeroes it, mgmc_set_rhs re-detects it: mgmc_handle::f0_zero).  Where every chain's f is
+// all-bits-zero, the cycle's fine z-marching sweeps and the 7-point z-marching residual + restriction run
+// their FZ instances, which take the constant +0.0 instead of streaming 8 B per unknown of zeros from HBM
+// (512^3: 1.07 GB per pass, three passes per cycle).  Same values: the stored zero is +0.0, so is the
+// constant, and the arithmetic keeps the add.  Not on a level with a low-rank part (its f is patched), not
+// the small residual kernel (a z-sweep level has nx >= 64, its coarse level nx >= 32: never small), and only
+// the cycle's ops: the stand-alone entry points take the caller's f.
+// (the conditions themselves: mgmc_rhs_zero.hpp, host-only and tested on the CPU)
+static RhsZeroOp rhs_zero_op(const mgmc_handle* h, const Op& op) {
+    const Level& lv = h->levels[op.level];
+    const bool has_coarse = op.level + 1 < (int)h->levels.size();
+    return RhsZeroOp{op.level, lv.zsweep, lv.lr.m, lv.spec.npoints, !(lv.paths & PATH_NO_ZRESTRICT),
+                     has_coarse ? h->levels[op.level + 1].L.nx : 0, tune::ZR_SMALL_NX, op.zpre};
+}
+// returns whether any op's mark changed (the graphs embed the kernel choice: the caller rebuilds them)
+bool mark_rhs_zero(mgmc_handle* h) {
+    bool changed = false;
+    for (Op& op : h->ops) {
+        const int z = (op.kind == OP_SWEEP && rhs_zero_sweep_ok(h->f0_zero, rhs_zero_op(h, op))) ||
+                              (op.kind == OP_RESIDUAL_RESTRICT && rhs_zero_residual_ok(h->f0_zero, rhs_zero_op(h, op)))
+                          ? 1
+                          : 0;
+        changed = changed || z != op.fzero;
+        op.fzero = z;
+    }
+    return changed;
+}
+
 // A tail launch runs one workgroup on one CU (512^3: 40-43 us); the rest of the chip is idle meanwhile.
 // Its spare workgroups draw the Box-Muller pairs of the sweeps that follow it instead: for every 3D
 // Galerkin level swept by quad passes (not a field level; with or without a low-rank part), the first sweep on that
@@ -1676,6 +1721,7 @@ int build_tails(mgmc_handle* h) {
     int rc = build_tails_only(h);
     if (rc == MGMC_OK) fuse_sweep_restrict(h);
     if (rc == MGMC_OK) mark_zero_inputs(h);
+    if (rc == MGMC_OK) mark_rhs_zero(h);
     if (rc == MGMC_OK) rc = plan_drawn_noise(h);
     return rc;
 }
@@ -1707,7 +1753,7 @@ void enqueue_ops(mgmc_handle* h, size_t begin, size_t end, hipStream_t s) {
                     const Level* lc = op.prolong ? &h->levels[op.level + 1] : nullptr;
                     xo = lv.buf(1 - op.src);
                     launch_zsweep(lv, lv.buf(op.src), xo, fs, g, op.direction, lc, lc ? lc->x : nullptr,
-                                  h->cfg.coarse_scaling, s, nch, lrr.e ? &lrr : nullptr);
+                                  h->cfg.coarse_scaling, s, nch, lrr.e ? &lrr : nullptr, op.fzero != 0);
                 } else if (lv.quads) {
                     xo = lv.buf(1 - op.src);
                     launch_quads(lv, lv.buf(op.src), xo, fs, g, op.direction, s, nch, op.xzero != 0, op.pnz);
@@ -1772,7 +1818,7 @@ void enqueue_ops(mgmc_handle* h, size_t begin, size_t end, hipStream_t s) {
                         pnl.sample = sample;
                     }
                     launch_residual_restrict(lv, lc, lv.buf(op.src), fr, lc.f, lc.x, 1, s, nch, nullptr, op.xzero != 0,
-                                             lrr.e ? &lrr : nullptr, op.pn_dst ? &pnl : nullptr);
+                                             lrr.e ? &lrr : nullptr, op.pn_dst ? &pnl : nullptr, op.fzero != 0);
                     if (op.xzero && h->poison)  // (debug) the skipped x_c write leaves stale values: make them NaN
                         for (int c = 0; c < nch; ++c)
                             hipLaunchKernelGGL(k_poison_interior, dim3((lc.L.nx - 1 + 255) / 256, lc.L.ny - 1,
@@ -2596,6 +2642,12 @@ int mgmc_level_kernels(const mgmc_handle* h, int level, char* out, size_t n) {
     if (!res.empty()) text += ";residual_restrict=" + res;
     // the low-rank path of a posterior level (mgmc_lowrank.hpp; rhs_inplace: the sweeps and the
     // residual above run their LRF instances, f + e read in place)
+    // the level's cycle ops run the zero-right-hand-side instances (mark_rhs_zero: level 0, f all +0.0)
+    for (const Op& op : h->ops)
+        if (op.level == level && op.fzero) {
+            text += ";rhs=zero";
+            break;
+        }
     if (lv.lr.m > 0)
         text += std::string(";lowrank=") + (lv.lr.rhs_inplace ? "dense,rhs_inplace" : lv.lr.dense_path ? "dense"
                                              : lv.lr.small ? "small" : "rows");
@@ -2618,10 +2670,26 @@ static int put_fine(mgmc_handle* h, double* v, int c, const double* host, size_t
     return MGMC_OK;
 }
 
+// Every write of level 0's f goes through here (mgmc_apply too).  The upload is still in lex_tmp (every
+// chain gets the same vector): its bit-pattern OR, read back with the synchronisation below, says
+// whether f is all-bits-zero; when that changes, the ops' marks and the graphs follow (mark_rhs_zero).
 int mgmc_set_rhs(mgmc_handle* h, const double* f, size_t n) {
     int rc = put_fine(h, h ? h->levels[0].f : nullptr, -1, f, n, "rhs");
     if (rc) return rc;
+    unsigned long long bits = 0;
+    unsigned long long* word = reinterpret_cast<unsigned long long*>(h->ctrl + 7);
+    HIPCHK(h, hipMemsetAsync(word, 0, sizeof(*word), h->stream));
+    const int nblk = (int)std::min<size_t>((n + 255) / 256, (size_t)16 * h->levels[0].num_cu);
+    hipLaunchKernelGGL(k_or_bits, dim3(nblk), dim3(256), 0, h->stream,
+                       reinterpret_cast<const unsigned long long*>(h->lex_tmp), (long long)n, word);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(&bits, word, sizeof(bits), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    const bool zero = rhs_bits_all_zero(bits);
+    if (zero != h->f0_zero) {
+        h->f0_zero = zero;
+        if (mark_rhs_zero(h)) return build_graphs(h);
+    }
     return MGMC_OK;
 }
 

@@ -44,6 +44,7 @@ static_assert(MGMC_LAYOUT_POINT == mgmc::LF_POINT && MGMC_LAYOUT_PAIRS == mgmc::
 #include "mgmc_cholesky.hpp"
 #include "mgmc_field.hpp"
 #include "mgmc_operators.hpp"
+#include "mgmc_rhs_zero.hpp"
 
 using namespace mgmc;
 
@@ -83,6 +84,8 @@ struct Op {
     int xzero = 0;           // OP_SWEEP: its input x is known zero (the restriction before it zeroed the level, nothing
                              // wrote it since): the kernel takes zeros instead of loading it (mark_zero_inputs);
                              // OP_RESIDUAL_RESTRICT: so the coarse x is not written at all
+    int fzero = 0;           // OP_SWEEP / OP_RESIDUAL_RESTRICT on level 0: the right-hand side is known to be all
+                             // +0.0 (mgmc_handle::f0_zero): the kernel's FZ instance does not load it (mark_rhs_zero)
     int zpre = 0;            // OP_SWEEP_RESTRICT: also draws the next OP_COARSE_LDS's noise into mgmc_handle::zbuf;
                              // OP_COARSE_LDS: reads it from there; OP_RESIDUAL_RESTRICT: 1 + the index of
                              // the OP_TAIL after it whose noise its spare workgroups draw
@@ -282,6 +285,9 @@ struct mgmc_handle {
     std::vector<Level> levels;
     hipStream_t stream = nullptr;
     uint64_t* ctrl = nullptr;       // [0] sample index [1] series length [2] qoi index [3] scratch sample
+                                    // [5] non-finite guard [6] its vertex [7] bit-pattern OR of an uploaded f
+    bool f0_zero = true;            // level 0's f is all-bits-zero for every chain: true from mgmc_create's
+                                    // memset on, re-detected by every mgmc_set_rhs (k_or_bits into ctrl[7])
     double* mom = nullptr;          // running (n, mean, M2, pad) per chain
     double* series = nullptr;
     uint64_t series_cap = 0;
@@ -401,7 +407,8 @@ void launch_sweep(const Level& lv, double* x, const double* f, const GibbsArg& g
 bool zres_lrf_capable(const Level& lf, const Level& lc);
 void launch_residual_restrict(const Level& lf, const Level& lc, const double* x, const double* f, double* fc,
                               double* xc, int zero_xc, hipStream_t s, int nch = 1, const TailNoiseLaunch* tn = nullptr,
-                              bool skip_xc = false, const LRRhsArg* lr = nullptr, const PreNoiseLaunch* pn = nullptr);
+                              bool skip_xc = false, const LRRhsArg* lr = nullptr, const PreNoiseLaunch* pn = nullptr,
+                              bool fzero = false);
 bool zres_draws_noise(const Level& lf, const Level& lc);
 void launch_prolongate(const Level& lf, const Level& lc, double* x, const double* xc, double alpha, hipStream_t s,
                        int nch = 1);
@@ -416,6 +423,7 @@ void launch_coarse_chol(const mgmc_handle* h, const Level& lv, const double* f, 
 Layout tail_layout(const Layout& L);
 void build_ops(mgmc_handle* h);
 int build_tails(mgmc_handle* h);
+bool mark_rhs_zero(mgmc_handle* h);
 int build_graphs(mgmc_handle* h);
 void destroy_graphs(mgmc_handle* h);
 int ensure_scratch(mgmc_handle* h, int level);

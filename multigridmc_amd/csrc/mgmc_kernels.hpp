@@ -759,6 +759,17 @@ __global__ void __launch_bounds__(256) k_operator_apply(Layout L, const double* 
 }
 
 // ---- reference (lexicographic interior) layout <-> padded layout ----
+// bit-pattern OR of v[0 .. n) into *out (mgmc_set_rhs: is the uploaded right-hand side all-bits-zero?
+// -0.0, denormals and NaN have bits set and count as non-zero)
+static __global__ void __launch_bounds__(256) k_or_bits(const unsigned long long* __restrict__ v, long long n,
+                                                 unsigned long long* __restrict__ out) {
+    unsigned long long acc = 0;
+    const long long stride = (long long)gridDim.x * 256;
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < n; q += stride) acc |= v[q];
+    for (int o = 32; o > 0; o >>= 1) acc |= __shfl_xor(acc, o);
+    if ((threadIdx.x & 63) == 0 && acc) atomicOr(out, acc);
+}
+
 template <int DIM>
 __global__ void __launch_bounds__(256) k_pack(Layout L, const double* __restrict__ lex, double* __restrict__ pad) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x + 1;

@@ -76,9 +76,12 @@ __device__ __forceinline__ void zr_plane12(uint32_t base, double (&v)[12]) {
 
 // SYM: a fold level (reflection-symmetric 27-point stencil): the residual's sum is fold27's
 // LRF: a low-rank level whose right-hand side is read in place (a.lr: f + e, lr_rhs_pair)
-template <int NPTS, int CX, int CY, int NT, bool ZN = false, bool SYM = false, bool LRF = false>
+// FZ: the right-hand side is identically +0.0 (prior sampling, mgmc_capi.hip mark_rhs_zero): f is not
+// loaded, r = 0.0 - A x with the literal (not -A x: the sign of an exact zero); not with LRF
+template <int NPTS, int CX, int CY, int NT, bool ZN = false, bool SYM = false, bool LRF = false, bool FZ = false>
 __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NPTS == 27 && SYM && CX >= 48 ? tune::ZR27_MINW : 1)))
 k_zresrestrict(ZRestrictArgs a) {
+    static_assert(!(LRF && FZ), "a patched right-hand side is not zero");
     if (ZN && (int)blockIdx.x >= a.nblk_main) {  // the tail's noise (see ZRestrictArgs)
         const int ch = batch_chain();
         RngKey key = a.key;
@@ -125,7 +128,7 @@ k_zresrestrict(ZRestrictArgs a) {
     {  // batched chains (blockIdx.z)
         const int ch = batch_chain();
         a.x += ch * a.csf;
-        a.f += ch * a.csf;
+        if (!FZ) a.f += ch * a.csf;
         a.fc += ch * a.csc;
         a.xc += ch * a.csc;
         if (LRF) a.lr.e += ch;
@@ -234,6 +237,7 @@ k_zresrestrict(ZRestrictArgs a) {
             }
     };
     auto issue_f = [&](int k) {
+        if constexpr (FZ) return;  // (pf is never read)
         const double* base = plane_ptr(a.f, k > kf_last ? kf_last : k);
 #pragma unroll
         for (int u = 0; u < NLR; ++u) pf[u] = *reinterpret_cast<const double2*>(base + roff[u]);
@@ -303,7 +307,8 @@ k_zresrestrict(ZRestrictArgs a) {
                     }
                 }
             }
-            double2 f = fv[u];
+            double2 f = make_double2(0.0, 0.0);  // (FZ: the constant)
+            if constexpr (!FZ) f = fv[u];
             if constexpr (LRF) f = lr_rhs_pair(f, lre);
             rs[rlds[u]] = (kin && (rflag[u] & 1)) ? f.x - y0 : 0.0;
             rs[rlds[u] + RP] = (kin && (rflag[u] & 2)) ? f.y - y1 : 0.0;

@@ -70,6 +70,10 @@ struct ZItem {
 // fma rounds once like the separate add and the bits are the same.
 // MINW: minimum waves per SIMD the register allocation must allow (1 = unconstrained)
 // LRF: a low-rank level whose right-hand side is read in place (a.lr: f + e, lr_rhs_pair)
+// FZ: the right-hand side is identically +0.0 (prior sampling: f = A 0, mgmc_capi.hip mark_rhs_zero): no
+// load of f is issued and no register holds it; the updates are the same instructions with the literal
+// +0.0 in its place (fma(sd, z, 0.0), not sd * z: the two differ in the sign of an exact zero), so the
+// bits are those of the general instance reading zeros.  Not with LRF.
 struct RunE0 {
     int value;
 };
@@ -78,9 +82,10 @@ struct RunE0 {
 constexpr int zs_threads(int TY) { return 256 * ((TY / 2 + 2 + 3) / 4); }
 
 // XP must be 32 (a wave = two rows of 32 pairs); TY a multiple of 4, <= 32
-template <int XP, int TY, int NT, int PROLONG, int MINW, bool LRF = false>
+template <int XP, int TY, int NT, int PROLONG, int MINW, bool LRF = false, bool FZ = false>
 __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MINW))) k_zsweep_rb7(ZSweepArgs a) {
     static_assert(XP == 32 && TY % 4 == 0 && TY <= 32 && NT == zs_threads(TY), "tile shape");
+    static_assert(!(LRF && FZ), "a patched right-hand side is not zero");
     // pairs per LDS row: positions [2*q0-1, 2*q0+2*XP+2] -- the core pairs and one halo pair per side.
     // The halo ring's column items need only their element next to the tile (the even one on the left,
     // the odd one on the right), whose x neighbours are staged; their other element's update reads a
@@ -119,7 +124,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MINW)))
         const int ch = batch_chain();
         a.xin += ch * a.cs;
         a.xout += ch * a.cs;
-        a.f += ch * a.cs;
+        if (!FZ) a.f += ch * a.cs;
         if (PROLONG) a.xc += ch * a.csc;
         a.G.key = chain_key(a.G, ch);
         if (LRF) a.lr.e += ch;
@@ -439,13 +444,16 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MINW)))
                 (void)fnxt;
             } else {
                 issue_x(p + 2 * dz, Bp{});
-                if (active_wave) fnxt = load_f(p + dz);
+                if constexpr (!FZ) {
+                    if (active_wave) fnxt = load_f(p + dz);
+                }
             }
             __syncthreads();
             // first colour on plane p: c = fma(sd, z, f), x = fma(omega/diag, c - S, x); the second
             // colour's right-hand side of the pair, c' = fma(sd, z', f')
             if (interior_plane(p) && active_wave) {
-                double2 fv = fcur;
+                double2 fv = make_double2(0.0, 0.0);  // (FZ: the constant)
+                if constexpr (!FZ) fv = fcur;
                 if constexpr (LRF) fv = lr_rhs_pair(fv, lre);
                 if (inf) {
                     const double res = row_sum(p, o1, e, xs[slot(p - 1) * PS + o1]);
@@ -455,7 +463,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MINW)))
                 }
                 pk_out = fma(sd, e ? z.x : z.y, e ? fv.x : fv.y);
             }
-            if constexpr (PF2) fcur = load_f(p + 2);  // this step's f is used up: the registers take f(p+2)
+            if constexpr (PF2 && !FZ) fcur = load_f(p + 2);  // this step's f is used up: the registers take f(p+2)
             __syncthreads();
             // second colour on plane k = p-1 (DN: p+1; its element is e: the parity flips with the plane)
             const int k = p - dz;
@@ -486,7 +494,9 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MINW)))
         double2 fA = make_double2(0.0, 0.0), fB = make_double2(0.0, 0.0);
         double pkA = 0.0, pkB = 0.0;
         const int pst = DN ? k1 : k0 - 1;  // first step's plane
-        if constexpr (PF2) {
+        if constexpr (FZ) {
+            // (no f in flight: fA, fB are never read)
+        } else if constexpr (PF2) {
             fA = load_f(k0 - 1);
             fB = load_f(k0);
         } else if (active_wave) {

@@ -600,7 +600,11 @@ class MultigridMCSampler:
         """The kernels the handle runs on a level (mgmc_level_kernels): {"sweep": ..., "post_sweep": ...,
         "residual_restrict": ..., "lowrank": ..., "noise": ...} ("lowrank" on posterior levels: "small",
         "rows", "dense" or "dense,rhs_inplace"; "noise": "restriction", "tail" or "restriction+tail" when sweeps
-        of the level read Box-Muller pairs drawn by the restriction launch before them / a tail launch)"""
+        of the level read Box-Muller pairs drawn by the restriction launch before them / a tail launch;
+        "rhs": "zero", on level 0 only, when its right-hand side is all +0.0 -- as created, or after
+        fix_rhs / apply with zeros; -0.0, denormals and NaN do not count -- and the cycle's z-marching sweeps
+        and residual + restriction take it as a constant instead of reading it: same bits, a third fewer
+        bytes; the key is absent otherwise)"""
         buf = ctypes.create_string_buffer(512)
         self._chk(self.lib.mgmc_level_kernels(self.handle, int(level), buf, 512))
         return dict(kv.split("=", 1) for kv in buf.value.decode().split(";"))

@@ -5,7 +5,7 @@ MI355X_MICROARCH.md's HBM section prescribes (KiB counters, FETCH_SIZE x 2 on gf
 per lane loads these kernels issue; WRITE_SIZE exact).  Algorithmic bytes per launch are given for
 the kernels SURVEY.md section 8(d) prices (n = fine cells):
   fine sweeps 24 B x N0 (+ 8 B x N1 with the fused prolongation), fine residual + restriction
-  16 B x N0 + 16 B x N1, level-1 half-sweep 12 B x N1 (half of a 24 B sweep), level-1 residual +
+  16 B x N0 + 16 B x N1 (the zero-right-hand-side instances, last template argument true: 8 B x N0 less), level-1 half-sweep 12 B x N1 (half of a 24 B sweep), level-1 residual +
   restriction 16 B x N1 + 16 B x N2, level-2 -> 1 prolongation 16 B x N1 + 8 B x N2.
 
 usage: pmc_by_kernel.py <dir>/pmc_FETCH_SIZE <dir>/pmc_WRITE_SIZE [n]
@@ -39,9 +39,11 @@ def main():
         algo = None
         if name.startswith("k_zsweep_rb7"):
             prolong = name.split(",")[3].strip() != "0"
-            algo = 24.0 * N[0] + (8.0 * N[1] if prolong else 0.0)
+            fz = len(name.split(",")) >= 7 and name.rstrip("> ").endswith("true")
+            algo = (16.0 if fz else 24.0) * N[0] + (8.0 * N[1] if prolong else 0.0)
         elif name.startswith("k_zresrestrict<7"):
-            algo = 16.0 * N[0] + 16.0 * N[1]
+            fz = len(name.split(",")) >= 8 and name.rstrip("> ").endswith("true")
+            algo = (8.0 if fz else 16.0) * N[0] + 16.0 * N[1]
         elif name.startswith("k_jsweep_half<128"):
             algo = 12.0 * N[1]
         elif name.startswith("k_zresrestrict<27, 64") and fb > 0.2 * 16.0 * N[1]:

@@ -14,9 +14,11 @@ import re
 import subprocess
 import sys
 
-# <XP, TY, NT, PROLONG, MINW[, LRF]>: the prior's instances (LRF = false, the low-rank posterior's in-place
-# right-hand side: not part of the bench)
-KERNEL = re.compile(r"k_zsweep_rb7<\s*(\d+),\s*(\d+),\s*(\d+),\s*(\d+),\s*(\d+)\s*(?:,\s*false\s*)?>")
+# <XP, TY, NT, PROLONG, MINW[, LRF[, FZ]]>: the prior's instances (LRF = false, the low-rank posterior's in-place
+# right-hand side: not part of the bench), general or with the zero right-hand side taken as a constant (FZ =
+# true: 16 B per unknown instead of 24)
+KERNEL = re.compile(r"k_zsweep_rb7<\s*(\d+),\s*(\d+),\s*(\d+),\s*(\d+),\s*(\d+)\s*"
+                    r"(?:,\s*false\s*(?:,\s*(false|true)\s*)?)?>")
 
 
 def per_launch(path, post):
@@ -25,8 +27,8 @@ def per_launch(path, post):
         m = KERNEL.search(r["Kernel_Name"])
         if m and (int(m.group(4)) > 0) == post:
             vals.append(float(r["Counter_Value"]))
-            name = m.group(0)
-    return sum(vals) / len(vals), len(vals), name
+            name, fz = m.group(0), m.group(6) == "true"
+    return sum(vals) / len(vals), len(vals), name, fz
 
 
 def main():
@@ -37,14 +39,15 @@ def main():
     n0 = (n - 1) ** 3
     n1 = (n // 2 - 1) ** 3
     out = {"n": n, "head": head, "date": datetime.date.today().isoformat(),
-           "source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE (separate passes) of scripts/vcycle_once.py",
+           "source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes, counters only) of scripts/vcycle_once.py",
            "correction": "FETCH_SIZE x2 (gfx950, 16 B/lane reads), KiB -> bytes x1024 (MI355X_MICROARCH.md HBM section)"}
-    for key, post, algo in (("pre_sweep", False, 24.0 * n0), ("post_sweep", True, 24.0 * n0 + 8.0 * n1)):
-        fetch_kib, nf, name = per_launch(f"{src}/pmc_FETCH_SIZE/pmc_counter_collection.csv", post)
-        write_kib, nw, _ = per_launch(f"{src}/pmc_WRITE_SIZE/pmc_counter_collection.csv", post)
+    for key, post, extra in (("pre_sweep", False, 0.0), ("post_sweep", True, 8.0 * n1)):
+        fetch_kib, nf, name, fz = per_launch(f"{src}/pmc_FETCH_SIZE/pmc_counter_collection.csv", post)
+        write_kib, nw, _, _ = per_launch(f"{src}/pmc_WRITE_SIZE/pmc_counter_collection.csv", post)
+        algo = (16.0 if fz else 24.0) * n0 + extra
         fetch = 2.0 * fetch_kib * 1024.0
         write = write_kib * 1024.0
-        out[key] = {"kernel": name, "launches": [nf, nw], "fetch_size_kib_raw": fetch_kib,
+        out[key] = {"kernel": name, "rhs_zero": fz, "launches": [nf, nw], "fetch_size_kib_raw": fetch_kib,
                     "write_size_kib_raw": write_kib, "fetch_bytes_corrected": fetch, "write_bytes": write,
                     "hbm_bytes_per_launch": fetch + write, "algorithmic_bytes_per_launch": algo,
                     "traffic_over_algorithmic": (fetch + write) / algo}
