@@ -245,6 +245,13 @@ int mgmc_lowrank_info(const mgmc_handle* h, int level, int direction, int* m, in
  * tests can drive mgmc_set_lowrank's rollback (a failed restore leaves the handle refusing the cycle
  * and solver calls until a later mgmc_set_lowrank succeeds).  n = 0 clears it. */
 int mgmc_debug_fail_coarse_factor(mgmc_handle* h, int n);
+/* testing hook: measures the LDS poison of MGMC_POISON=1 (the NaN fill launched before every op of the cycle
+ * graph and every LDS-using launch of the per-level calls).  Launches that fill (nothing without
+ * MGMC_POISON), then *nwg = 2 x (compute units) probe workgroups of the fill's footprint (80 KB of LDS), which
+ * read every word of their LDS without writing any.  *nwg_all_nan = the probe workgroups that read NaN in
+ * every word, *min_nan_fraction = the smallest fraction of NaN words any of them read.  Full coverage is
+ * *nwg_all_nan == *nwg; without MGMC_POISON the call returns MGMC_OK and the counts say what the LDS held. */
+int mgmc_debug_lds_probe(mgmc_handle* h, int64_t* nwg, int64_t* nwg_all_nan, double* min_nan_fraction);
 
 /* ---- Sampler interface (host buffers, reference layout) ---- */
 int mgmc_set_rhs(mgmc_handle* h, const double* f, size_t n);       /* fix_rhs: f stays in HBM */

@@ -28,6 +28,29 @@ __global__ void __launch_bounds__(1024) k_lds_poison() {
     // a read the compiler cannot drop keeps the stores alive
     if (lds[(threadIdx.x * 7) % LDS_POISON_DOUBLES] == 0.0) asm volatile("" ::: "memory");
 }
+// (debug, MGMC_POISON=1 only) the launches that follow on s start on NaN-filled LDS: every op of the
+// cycle graph and every LDS-using launch of the stand-alone entry points is preceded by this
+inline void lds_poison(const mgmc_handle* h, const Level& lv, hipStream_t s) {
+    if (!h->poison) return;
+    hipLaunchKernelGGL(k_lds_poison, dim3(8 * lv.num_cu), dim3(1024), LDS_POISON_DOUBLES * sizeof(double), s);
+}
+// The poison's measure (mgmc_debug_lds_probe): a workgroup of k_lds_poison's footprint reads every word of
+// its LDS allocation without writing any; each wavefront sums its lanes' counts of NaN words by shuffles and
+// lane 0 stores the sum to cnt[16 * blockIdx.x + wave] (the host adds a workgroup's 16).  Reading LDS
+// nothing wrote is harmless; volatile keeps the loads.
+constexpr int LDS_PROBE_WAVES = 1024 / 64;
+__global__ void __launch_bounds__(1024) k_lds_probe(int* __restrict__ cnt) {
+    extern __shared__ double lds[];
+    const volatile double* v = lds;
+    int n = 0;
+    for (int q = threadIdx.x; q < LDS_POISON_DOUBLES; q += blockDim.x) {
+        const double w = v[q];
+        n += w != w ? 1 : 0;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) n += __shfl_xor(n, off, 64);
+    if ((threadIdx.x & 63) == 0) cnt[LDS_PROBE_WAVES * blockIdx.x + (threadIdx.x >> 6)] = n;
+}
 // NaN into every interior vertex of one level vector (the zero boundary and pad stay zero): in poison
 // mode the coarse x a restriction with Op::xzero leaves unwritten (it holds the previous cycle's
 // values until the post-sweep rewrites it) -- a later op that read it would trip the guard
@@ -1012,6 +1035,7 @@ void launch_operator_apply(const mgmc_handle* h, const Level& lv, const double* 
     else
         hipLaunchKernelGGL((k_operator_apply<2, 9>), grid, block, 0, s, lv.L, xs, ys, lv.S);
     if (lv.lr.m > 0) {  // y += B (Sigma^{-1} B^T x)  (linear_operator.hh:71-75)
+        lds_poison(h, lv, s);
         lr_dots(lv, xs, LR_SCALE_INV, s);
         lr_rhs(h, lv, LR_PATCH_APPLY, ys, 0, h->ctrl + 3, s);
     }
@@ -1732,8 +1756,7 @@ void enqueue_ops(mgmc_handle* h, size_t begin, size_t end, hipStream_t s) {
     for (size_t q = begin; q < end; ++q) {
         const Op& op = h->ops[q];
         Level& lv = h->levels[op.level];
-        if (h->poison)  // (debug: poison_fill) the op's kernels start on NaN-filled LDS
-            hipLaunchKernelGGL(k_lds_poison, dim3(8 * lv.num_cu), dim3(1024), LDS_POISON_DOUBLES * sizeof(double), s);
+        lds_poison(h, lv, s);  // (debug: poison_fill) the op's kernels start on NaN-filled LDS
         switch (op.kind) {
             case OP_SWEEP: {
                 GibbsArg g = make_gibbs(h, lv, op.tag, 0, sample);
@@ -2912,6 +2935,7 @@ int mgmc_operator_apply(mgmc_handle* h, int level, const double* x, double* y) {
     if ((rc = ensure_scratch(h, level))) return rc;
     Level& lv = h->levels[level];
     if ((rc = upload(h, level, x, lv.scratch[0]))) return rc;
+    lds_poison(h, lv, h->stream);
     launch_operator_apply(h, lv, lv.scratch[0], lv.scratch[1], h->stream);
     HIPCHK(h, hipGetLastError());
     return download(h, level, lv.scratch[1], y);
@@ -2935,9 +2959,7 @@ static int sweep_component(mgmc_handle* h, int level, int direction, int nsweeps
         GibbsArg g = make_gibbs(h, lv, tag + (uint32_t)s, 0, h->ctrl + 3);
         double* fb = lv.scratch[0];
         if (lr && noise) fb = lr_rhs(h, lv, LR_PATCH_NOISE, lv.scratch[0], tag + (uint32_t)s, h->ctrl + 3, h->stream);
-        if (h->poison)  // (debug: as enqueue_ops) the sweep starts on NaN-filled LDS
-            hipLaunchKernelGGL(k_lds_poison, dim3(8 * lv.num_cu), dim3(1024), LDS_POISON_DOUBLES * sizeof(double),
-                               h->stream);
+        lds_poison(h, lv, h->stream);  // (debug: as enqueue_ops) the sweep starts on NaN-filled LDS
         if (noise && lv.zsweep) {  // the fused z-marching kernel of the V-cycle (out of place)
             launch_zsweep(lv, lv.scratch[cur], lv.scratch[3 - cur], fb, g, direction, nullptr, nullptr, 0.0, h->stream);
             cur = 3 - cur;
@@ -2952,7 +2974,10 @@ static int sweep_component(mgmc_handle* h, int level, int direction, int nsweeps
         } else {
             launch_sweep(lv, lv.scratch[cur], fb, g, direction, noise, h->stream);
         }
-        if (lr) lr_fix(lv, lv.scratch[cur], direction, noise && fb == lv.scratch[0] ? lv.scratch[0] : nullptr, h->stream);
+        if (lr) {
+            lds_poison(h, lv, h->stream);
+            lr_fix(lv, lv.scratch[cur], direction, noise && fb == lv.scratch[0] ? lv.scratch[0] : nullptr, h->stream);
+        }
     }
     HIPCHK(h, hipGetLastError());
     return download(h, level, lv.scratch[cur], x);
@@ -2976,8 +3001,12 @@ static int smoother_sequence(mgmc_handle* h, int level, const std::vector<std::p
     if ((rc = upload(h, level, x, lv.scratch[1]))) return rc;
     for (const auto& st : seq) {
         GibbsArg g = make_gibbs(h, lv, 0, 0, h->ctrl + 3);
+        lds_poison(h, lv, h->stream);
         launch_sweep(lv, lv.scratch[1], lv.scratch[0], g, st.first, false, h->stream);
-        if (st.second && lv.lr.m > 0) lr_fix(lv, lv.scratch[1], st.first, nullptr, h->stream);
+        if (st.second && lv.lr.m > 0) {
+            lds_poison(h, lv, h->stream);
+            lr_fix(lv, lv.scratch[1], st.first, nullptr, h->stream);
+        }
     }
     HIPCHK(h, hipGetLastError());
     return download(h, level, lv.scratch[1], x);
@@ -3024,6 +3053,7 @@ int mgmc_restrict(mgmc_handle* h, int level, const double* r, double* rc_out) {
     if ((rc = upload(h, level, r, lf.scratch[0]))) return rc;
     dim3 block(64, 4, 1);
     dim3 grid = grid3(lc.L.nx - 1, lc.L.ny - 1, lf.spec.dim == 3 ? lc.L.nz - 1 : 1, block);
+    lds_poison(h, lf, h->stream);
     if (lf.spec.dim == 3)
         hipLaunchKernelGGL((k_restrict<3>), grid, block, 0, h->stream, lf.L, lc.L, (const double*)lf.scratch[0],
                            lc.scratch[0]);
@@ -3044,6 +3074,7 @@ int mgmc_prolongate_add(mgmc_handle* h, int level, double alpha, const double* x
     Level& lc = h->levels[level + 1];
     if ((rc = upload(h, level + 1, xc, lc.scratch[0]))) return rc;
     if ((rc = upload(h, level, x, lf.scratch[0]))) return rc;
+    lds_poison(h, lf, h->stream);
     launch_prolongate(lf, lc, lf.scratch[0], lc.scratch[0], alpha, h->stream);
     HIPCHK(h, hipGetLastError());
     return download(h, level, lf.scratch[0], x);
@@ -3060,10 +3091,12 @@ int mgmc_residual_restrict(mgmc_handle* h, int level, const double* f, const dou
     if ((rc = upload(h, level, f, lf.scratch[0]))) return rc;
     if ((rc = upload(h, level, x, lf.scratch[1]))) return rc;
     double* fr = lf.scratch[0];
+    lds_poison(h, lf, h->stream);
     if (lf.lr.m > 0) {  // f - B Sigma^{-1} B^T x, then the residual kernel
         lr_dots(lf, lf.scratch[1], LR_SCALE_INV, h->stream);
         fr = lr_rhs(h, lf, LR_PATCH_RESIDUAL, lf.scratch[0], 0, h->ctrl + 3, h->stream);
     }
+    if (lf.lr.m > 0) lds_poison(h, lf, h->stream);  // (the low-rank launches above wrote LDS again)
     launch_residual_restrict(lf, lc, lf.scratch[1], fr, lc.scratch[0], lc.scratch[1], 1, h->stream);
     HIPCHK(h, hipGetLastError());
     return download(h, level + 1, lc.scratch[0], fc);
@@ -3102,6 +3135,7 @@ int mgmc_time_fine_sweeps(mgmc_handle* h, int nsweeps, float* ms) {
     for (int s = 0; s < nsweeps; ++s) {
         GibbsArg g = make_gibbs(h, lv, 0x80000000u + (uint32_t)s, 0, h->ctrl);
         const int dir = (s & 1) ? MGMC_BACKWARD : MGMC_FORWARD;
+        lds_poison(h, lv, h->stream);  // (debug only: the time then includes the fill)
         if (lv.zsweep) {
             launch_zsweep(lv, lv.scratch[cur], lv.scratch[3 - cur], lv.f, g, dir, nullptr, nullptr, 0.0, h->stream);
             cur = 3 - cur;
@@ -3118,6 +3152,40 @@ int mgmc_time_fine_sweeps(mgmc_handle* h, int nsweeps, float* ms) {
     HIPCHK(h, hipGetLastError());
     hipEventDestroy(e0);
     hipEventDestroy(e1);
+    return MGMC_OK;
+}
+
+int mgmc_debug_lds_probe(mgmc_handle* h, int64_t* nwg, int64_t* nwg_all_nan, double* min_nan_fraction) {
+    if (!h || !nwg || !nwg_all_nan || !min_nan_fraction) return fail(h, MGMC_E_INVALID, "null argument");
+    HIPCHK(h, hipSetDevice(h->device));
+    const Level& lv = h->levels[0];
+    const int n = 2 * lv.num_cu;  // the workgroups of this footprint one round of the device holds
+    const size_t bytes = (size_t)n * LDS_PROBE_WAVES * sizeof(int);
+    int* cnt = nullptr;
+    HIPCHK(h, hipMalloc(&cnt, bytes));
+    std::vector<int> host((size_t)n * LDS_PROBE_WAVES);
+    hipError_t e = hipMemsetAsync(cnt, 0, bytes, h->stream);
+    if (e == hipSuccess) {
+        lds_poison(h, lv, h->stream);  // (nothing without MGMC_POISON: the probe then counts what it finds)
+        hipLaunchKernelGGL(k_lds_probe, dim3(n), dim3(1024), LDS_POISON_DOUBLES * sizeof(double), h->stream, cnt);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(host.data(), cnt, bytes, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    hipFree(cnt);
+    HIPCHK(h, e);
+    int64_t all = 0;
+    int lo = LDS_POISON_DOUBLES;
+    for (int b = 0; b < n; ++b) {
+        int c = 0;
+        for (int w = 0; w < LDS_PROBE_WAVES; ++w) c += host[(size_t)b * LDS_PROBE_WAVES + w];
+        all += c == LDS_POISON_DOUBLES;
+        lo = std::min(lo, c);
+    }
+    *nwg = n;
+    *nwg_all_nan = all;
+    *min_nan_fraction = (double)lo / LDS_POISON_DOUBLES;
     return MGMC_OK;
 }
 

@@ -254,11 +254,15 @@ __global__ void __launch_bounds__(1024) k_sweep_quads(QuadPassArgs a) {
             for (int rr = 0; rr < NR; ++rr) {
                 const int dz = rr / 3 - 1, dy = rr % 3 - 1;
                 if (from_lds && dz == 0 && dy != 0) {  // the new first-pair rows of this plane
-                    const double* q = rowbuf + (lr + dy) * RW + 2 * m;
-                    w[rr][0] = q[0];
-                    w[rr][1] = q[1];
-                    w[rr][2] = q[2];
-                    w[rr][3] = q[3];
+                    // (lanes without a row here would read rows 2T+1, 2T+2, past the 2T+1 rows of rowbuf)
+                    w[rr][0] = w[rr][1] = w[rr][2] = w[rr][3] = 0.0;
+                    if (inrow) {
+                        const double* q = rowbuf + (lr + dy) * RW + 2 * m;
+                        w[rr][0] = q[0];
+                        w[rr][1] = q[1];
+                        w[rr][2] = q[2];
+                        w[rr][3] = q[3];
+                    }
                     continue;
                 }
                 const double l = lane_prev(mid[rr].y), r = lane_next(mid[rr].x);

@@ -370,8 +370,9 @@ inline int fail(mgmc_handle* h, int code, const std::string& msg) {
 
 // Debug poison (MGMC_POISON=1, read at mgmc_create*): every device buffer the library does not zero
 // or fill completely at allocation (noise buffers, the QoI series, dot partials, staging, solver
-// scratch) is filled with 0xFF bytes (a NaN pattern), and every op of a captured cycle graph is
-// preceded by k_lds_poison, which fills the LDS of every CU with NaN.  A kernel that reads device
+// scratch) is filled with 0xFF bytes (a NaN pattern), and every op of a captured cycle graph and every
+// LDS-using launch of the per-level entry points (mgmc_capi.hip lds_poison) is preceded by
+// k_lds_poison, which fills the LDS of every CU with NaN (measured: mgmc_debug_lds_probe).  A kernel that reads device
 // memory or LDS that no kernel of the cycle wrote -- recycled allocations, the previous kernel's LDS
 // -- then carries a NaN into the chain and the non-finite guard reports it (MGMC_E_NONFINITE).
 inline void poison_fill(const mgmc_handle* h, void* p, size_t bytes) {

@@ -440,6 +440,16 @@ class MultigridMCSampler:
         self._chk(self.lib.mgmc_lowrank_info(self.handle, int(level), int(direction), ctypes.byref(m), ctypes.byref(n)))
         return m.value, n.value
 
+    def debug_lds_probe(self) -> dict:
+        """Measure the LDS poison of MGMC_POISON=1 (mgmc_debug_lds_probe): the NaN fill, then probe workgroups
+        of its footprint that read their LDS without writing it.  {"nwg": probe workgroups, "nwg_all_nan":
+        those that read NaN in every word, "min_nan_fraction": the smallest NaN fraction one of them read}."""
+        nwg = ctypes.c_int64()
+        full = ctypes.c_int64()
+        frac = ctypes.c_double()
+        self._chk(self.lib.mgmc_debug_lds_probe(self.handle, ctypes.byref(nwg), ctypes.byref(full), ctypes.byref(frac)))
+        return {"nwg": nwg.value, "nwg_all_nan": full.value, "min_nan_fraction": frac.value}
+
     # -- lifetime --
     def close(self):
         if getattr(self, "handle", None):

@@ -20,6 +20,11 @@ int main(int argc, char** argv) {
         for (int l = 0; l < 4; ++l)
             std::printf("level %d n %d ndof %llu npoints %d ncolours %d centre %.17g\n", l, d[l].nx,
                         (unsigned long long)d[l].ndof, d[l].npoints, d[l].ncolours, d[l].stencil[13]);
+        // the debug entries link from C++ and refuse a null handle
+        int64_t nwg = 0, full = 0;
+        double frac = 0.0;
+        std::printf("debug %d %d\n", mgmc_debug_fail_coarse_factor(nullptr, 0) != MGMC_OK,
+                    mgmc_debug_lds_probe(nullptr, &nwg, &full, &frac) != MGMC_OK);
         return 0;
     }
     if (!std::strcmp(argv[1], "sample")) {

@@ -68,7 +68,7 @@ CONFIGS = {
     # j-marching half-sweeps (k_jsweep_half) on a short level 1 of 128-pair rows, SSOR, W-cycle
     "3d_jsweep_ssor_W": ((512, 44, 60), dict(nlevel=3, cycle=2, smoother="SSOR", npresmooth=2, omega=1.1)),
     # a tail (levels 3-4) followed by a 127 x 7 x 7 quad-pass level whose post-sweep reads the Box-Muller pairs
-    # the tail launch's spare workgroups drew (plan_post_noise), and a 255 x 15 x 15 j-marching level
+    # the tail launch's spare workgroups drew (plan_drawn_noise), and a 255 x 15 x 15 j-marching level
     "3d_jsweep_tail": ((512, 32, 32), dict(nlevel=5)),
     # dense Cholesky coarse sampler (CholeskySampler, x = G f + U xi on the coarsest level)
     "2d64_chol_W": ((64, 64), dict(nlevel=4, cycle=2, coarse_solver="Cholesky")),

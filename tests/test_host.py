@@ -28,6 +28,7 @@ def test_library_exports_every_header_symbol():
     lib = mg.load_library()
     syms = header_symbols()
     assert len(syms) >= 25
+    assert {"mgmc_debug_fail_coarse_factor", "mgmc_debug_lds_probe"} <= set(syms)
     bound = {name for name, _, _ in _native.SIGNATURES}
     for s in syms:
         assert hasattr(lib, s), f"{s} declared in include/mgmc.h but not exported"
@@ -307,6 +308,8 @@ def test_cpp_host_side_describe_and_loud_failure(tmp_path, asan):
         tok = line.split()
         assert int(tok[5]) == cfg_levels[level]["ndof"]
         assert float(tok[11]) == cfg_levels[level]["stencil"][13]
+    # mgmc_debug_fail_coarse_factor and mgmc_debug_lds_probe link from C++ and refuse a null handle
+    assert out[5] == "debug 1 1"
     hip = ctypes.CDLL("libamdhip64.so")
     n = ctypes.c_int(0)
     if hip.hipGetDeviceCount(ctypes.byref(n)) == 0 and n.value > 0:
