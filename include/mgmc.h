@@ -212,8 +212,10 @@ int mgmc_nchains(const mgmc_handle* h);
 int mgmc_destroy(mgmc_handle* h);
 int mgmc_level_desc_get(const mgmc_handle* h, int level, mgmc_level_desc* out);
 /* The kernels this handle runs on a level (ABI 5), as text "sweep=<kernel>[;post_sweep=<kernel>]
- * [;noise=<source>][;residual_restrict=<kernel>][;rhs=zero][;lowrank=<path>]", the keys in this order -- for
- * labels (bench.py) and profiles;
+ * [;noise=<source>][;residual_restrict=<kernel>][;rhs=zero][;lowrank=<path>][;quads=window]", the keys in this
+ * order -- for labels (bench.py) and profiles;
+ * quads=window: a 3D k_sweep_quads<3> level whose rows (nx/2 pairs, not a divisor of 64) run the three-load
+ * window instances; without the key such a level runs the lane-shift instances;
  * <source>: restriction | tail | restriction+tail -- sweeps of the level read Box-Muller pairs drawn by the
  * restriction launch before the first pre-sweep and / or a tail launch's spare workgroups;
  * rhs=zero, on level 0 only: the level's right-hand side is all +0.0 (prior sampling: as created, or after a

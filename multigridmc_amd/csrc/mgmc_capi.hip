@@ -359,6 +359,11 @@ void launch_jsweep(const Level& lv, const double* xin, double* xout, const doubl
     }
 }
 
+// 3D quad-pass rows of npair dividing 64 (127^3 / 63^3 / 31^3 ...): whole rows per wavefront, the window's outer
+// columns by lane shifts (k_sweep_quads LANES); every other row length takes the three-load window
+// (mgmc_level_kernels: quads=window)
+bool quads_lanes(int dim, int npair) { return dim == 3 && 64 % npair == 0 && tune::QUADS_LANES != 0; }
+
 // zb: the sweep's Box-Muller pairs, drawn by an earlier launch (Op::pnz, plan_drawn_noise; 3D quad-pass
 // levels, one chain; with xzero forward sweeps only)
 void launch_quads(const Level& lv, const double* xin, double* xout, const double* f, const GibbsArg& g, int direction,
@@ -387,7 +392,7 @@ void launch_quads(const Level& lv, const double* xin, double* xout, const double
     const int nt = npair * (a.T + 1);
     const size_t lds = (size_t)(2 * a.T + 1) * (lv.L.nx + 2) * sizeof(double);
     const bool fwd = direction == MGMC_FORWARD;
-    const bool lanes = dim == 3 && 64 % npair == 0 && tune::QUADS_LANES != 0;
+    const bool lanes = quads_lanes(dim, npair);
     a.jp1 = fwd ? 0 : 1;  // first pair: colours (0,1) / (4,5) forward, (7,6) / (3,2) backward
     const int nhalf = dim == 3 ? 2 : 1;
     for (int h = 0; h < nhalf; ++h) {
@@ -399,8 +404,7 @@ void launch_quads(const Level& lv, const double* xin, double* xout, const double
         const dim3 grid(a.nblk_y * nk, 1, nch);
         if (dim == 3) {
             // xzero (3D): the first half takes every x row as 0.0, the second its own planes' rows
-            // rows of npair dividing 64 (127^3 / 63^3 / 31^3 ...): whole rows per wavefront, the window's
-            // outer columns by lane shifts (k_sweep_quads LANES)
+            // lanes: quads_lanes above
 #define MGMC_QD_LAUNCH(SYMV, XZ)                                                                            \
     do {                                                                                                    \
         if (lanes) {                                                                                        \
@@ -2674,6 +2678,8 @@ int mgmc_level_kernels(const mgmc_handle* h, int level, char* out, size_t n) {
     if (lv.lr.m > 0)
         text += std::string(";lowrank=") + (lv.lr.rhs_inplace ? "dense,rhs_inplace" : lv.lr.dense_path ? "dense"
                                              : lv.lr.small ? "small" : "rows");
+    // a 3D quad-pass level whose row length takes the three-load window instances (quads_lanes)
+    if (sweep == "k_sweep_quads<3>" && !quads_lanes(dim, lv.L.nx / 2)) text += ";quads=window";
     snprintf(out, n, "%s", text.c_str());
     return MGMC_OK;
 }

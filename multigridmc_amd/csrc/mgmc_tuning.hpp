@@ -1,8 +1,10 @@
 // mgmc_tuning.hpp -- the library's launch-shape constants, in one place.
 //
 // Every value here is bitwise-neutral: it sets tile shapes, chunk depths, thread counts and launch
-// thresholds, never an arithmetic order, so the results do not depend on it (the -m gpu suite holds at
-// any setting; the layout check of mgmc_layout_check.hpp covers every shape).  The values are the ones
+// thresholds, never an arithmetic order, so the results do not depend on it (the -m gpu suite's bitwise
+// comparisons hold at any setting -- its label assertions name the instances the values below select, e.g.
+// quads=window on every 3D quad-pass level with QUADS_LANES = 0; the layout check of mgmc_layout_check.hpp
+// covers every shape).  The values are the ones
 // measured fastest on MI355X; the losing alternatives and their timings are in docs/HISTORY.md and
 // DESIGN.md 3i.  Timing experiments (scripts/build_exp.sh) build a copy of the sources with edited
 // values here; the product build has no override switches.

@@ -614,7 +614,9 @@ class MultigridMCSampler:
         "rhs": "zero", on level 0 only, when its right-hand side is all +0.0 -- as created, or after
         fix_rhs / apply with zeros; -0.0, denormals and NaN do not count -- and the cycle's z-marching sweeps
         and residual + restriction take it as a constant instead of reading it: same bits, a third fewer
-        bytes; the key is absent otherwise)"""
+        bytes; the key is absent otherwise; "quads": "window" on a 3D "k_sweep_quads<3>" level whose row
+        length -- nx/2 pairs, not a divisor of 64 -- selects the three-load window instances instead of the
+        lane-shift ones)"""
         buf = ctypes.create_string_buffer(512)
         self._chk(self.lib.mgmc_level_kernels(self.handle, int(level), buf, 512))
         return dict(kv.split("=", 1) for kv in buf.value.decode().split(";"))

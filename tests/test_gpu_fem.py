@@ -26,6 +26,8 @@ CONFIGS = {
     "3d32_chol": ((32, 32, 32), dict(nlevel=3, coarse_solver="Cholesky")),
     # j-marching half-sweeps on the 27-point fine level (256-pair rows) and level 1 (128-pair rows)
     "3d_jsweep": ((512, 24, 20), dict(nlevel=3, smoother="SSOR")),
+    # the 27-point fine level on the three-load window quad passes (24-pair rows: 64 % 24 != 0)
+    "3d_48x40x24": ((48, 40, 24), dict(nlevel=3)),
 }
 
 
@@ -116,4 +118,12 @@ def test_fem_jsweep_kernel_instances(hip_device):
     s, mc, p, lat = make("3d_jsweep")
     assert s.level_kernels(0)["sweep"] == "k_jsweep_half<256>"
     assert s.level_kernels(1)["sweep"] == "k_jsweep_half<128>"
+    s.close()
+
+
+def test_fem_window_quads_instance(hip_device):
+    """The 27-point fine level of 24-pair rows runs the quad passes' three-load window instances."""
+    s, mc, p, lat = make("3d_48x40x24")
+    k = s.level_kernels(0)
+    assert k["sweep"] == "k_sweep_quads<3>" and k.get("quads") == "window", k
     s.close()

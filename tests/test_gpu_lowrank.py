@@ -41,6 +41,8 @@ CONFIGS = {
                                (0.0, 5, True)),
     # ... the global average alone (m = 1: no local rows, every patch is the kernels' e)
     "3d128_global_only_inplace": ((128, 128, 128), dict(nlevel=3), (0.0, 0, True)),
+    # a low-rank level on the three-load window quad passes (level 1: 24-pair rows, 64 % 24 != 0)
+    "3d_96x48x48_points": ((96, 48, 48), dict(nlevel=3), (0.0, 4, False)),
 }
 TAIL_CONFIGS = ["2d64_ball_ssor_W", "3d32_points_tail_W", "3d48_ball_tail_ssor", "2d128_points_tail"]
 
@@ -92,6 +94,9 @@ def test_lowrank_cycles_bitwise(hip_device, name):
     if name in ("3d128_global_inplace_W", "3d128_global_only_inplace"):  # the path these configurations are here for
         assert s.level_kernels(0)["lowrank"] == "dense,rhs_inplace"
         assert s.level_kernels(1)["lowrank"] == "dense"
+    if name == "3d_96x48x48_points":
+        k = s.level_kernels(1)
+        assert k["sweep"] == "k_sweep_quads<3>" and k.get("quads") == "window" and "lowrank" in k, k
     rng = np.random.default_rng(11)
     f = rng.standard_normal(lat.Nvertex)
     x_dev = np.zeros(lat.Nvertex)

@@ -82,7 +82,34 @@ CONFIGS = {
     # ... 32-pair rows: 5 coarse rows per workgroup, the last workgroup partial (23 coarse rows); the
     # level sits in k_tail unless MGMC_DISABLE=tail (variant below)
     "2d_qr_cj5": ((128, 96), dict(nlevel=3, ncoarsesmooth=2)),
+    # ---- row lengths that are no powers of two (x fixes the thread layout) ----
+    # 24- and 12-pair rows (64 % npair != 0): the three-load window quad passes, 120-thread workgroups, known-zero
+    # input, post-sweep noise from the tail; k_zresrestrict<7,64,4> with one partial tile; tail of 12^3 and 6^3
+    "3d96_5lvl": ((96, 96, 96), dict(nlevel=5)),
+    # fine z-sweep of three 64-pair tiles, prolongation fused from a 96-wide coarse row; window quads of 48 pairs
+    # (240 threads) and of 24 pairs whose pre-sweep noise the 27-point restriction draws
+    "3d_192x48x48_5lvl": ((192, 48, 48), dict(nlevel=5)),
+    # five z-sweep tiles; level 1 of 80-pair rows: k_sweep_pairs<3> on its default path, 3 rows = 240 of 256 threads;
+    # k_zresrestrict<27,64,4> onto nx = 80
+    "3d_320x24x16": ((320, 24, 16), dict(nlevel=3)),
+    # k_zresrestrict<7,16,4> onto 11 coarse columns; a tail of 12 x 10 x 6 and 6 x 5 x 3 (odd extents)
+    "3d_24x20x12": ((24, 20, 12), dict(nlevel=3)),
+    # window quads of 20 pairs, backward (FIRST_ODD) instances, repeat visits of the W-cycle
+    "3d_80x48x40_ssor_W": ((80, 48, 40), dict(nlevel=3, cycle=2, smoother="SSOR", npresmooth=2, omega=1.1)),
+    # window quads of 34 pairs (238 threads) and 17 pairs (119 threads, odd pair count), restriction-drawn noise
+    # onto nx = 34, an odd 17^3 coarsest level
+    "3d136_4lvl": ((136, 136, 136), dict(nlevel=4)),
+    # k_rb2d with a 71-column last tile and a 7-row last tile; k_quads_restrict2d of 50 pairs (256 threads, CJ = 2,
+    # 56 idle); tail of 50 x 30 and 25 x 15
+    "2d_200x120_4lvl": ((200, 120), dict(nlevel=4)),
+    # three rb2d tiles; k_quads_restrict2d of 75 pairs (512 threads, CJ = 3, 62 idle), backward last pre-sweep;
+    # coarsest 75 x 50 (odd nx)
+    "2d_300x200_ssor": ((300, 200), dict(nlevel=3, smoother="SSOR")),
+    # one partial rb2d tile of 99 columns; a tail with 25-pair rows and an odd 25 x 15 coarsest level
+    "2d_100x60": ((100, 60), dict(nlevel=3)),
 }
+# the configurations above whose rows are no powers of two, registered in the component and sweep tests below
+ROW_LENGTHS = ["3d96_5lvl", "3d_192x48x48_5lvl", "3d_320x24x16", "3d_24x20x12", "2d_200x120_4lvl", "2d_300x200_ssor"]
 
 
 def test_normals_bitwise(hip_device):
@@ -98,7 +125,7 @@ def test_normals_bitwise(hip_device):
 
 
 @pytest.mark.parametrize("name", ["2d64_template_W", "3d16", "3d_aniso", "2d_aniso_ssor", "3d_zres7", "3d_zres27",
-                                  "3d_zres_lasttile", "3d128_zsweep"])
+                                  "3d_zres_lasttile", "3d128_zsweep"] + ROW_LENGTHS)
 def test_component_kernels_bitwise(hip_device, name):
     shape, kw = CONFIGS[name]
     s, p, lat = make(shape, **kw)
@@ -129,6 +156,8 @@ def test_component_kernels_bitwise(hip_device, name):
                 assert np.array_equal(d, faithful.residual_restrict(level, f, x))
     if name in ("3d16", "3d_aniso", "3d128_zsweep"):  # their Galerkin levels are reflection-symmetric
         assert folds == p.nlevel - 2
+    if name in ROW_LENGTHS:  # not reflection-symmetric bit for bit: every residual in the reference's CSR order
+        assert folds == 0
     s.close()
 
 
@@ -156,7 +185,7 @@ def test_fold_levels_reference_order_bitwise(hip_device, monkeypatch, name):
 
 
 @pytest.mark.parametrize("name", ["2d64_template_W", "3d16", "3d_aniso", "2d_aniso_ssor", "3d64_4lvl",
-                                  "3d128_zsweep", "3d_aniso_zsweep_ssor"])
+                                  "3d128_zsweep", "3d_aniso_zsweep_ssor"] + ROW_LENGTHS + ["3d_80x48x40_ssor_W"])
 def test_multicolour_sweeps_bitwise(hip_device, name):
     shape, kw = CONFIGS[name]
     s, p, lat = make(shape, **kw)
@@ -253,7 +282,16 @@ VARIANTS = [("fuse_prolong", "3d128_zsweep"), ("fuse_prolong", "3d_aniso_zsweep_
             ("fold", "3d16"), ("fold", "3d64_4lvl"), ("fold", "3d_zres27"), ("fold,tail", "3d64_4lvl"),
             ("fold,zrestrict", "3d32_W_ssor"),
             ("post_noise", "3d64_4lvl"), ("post_noise", "3d32_W_ssor"), ("post_noise", "3d_jsweep_tail"),
-            ("jsweep", "3d_jsweep_tail")]
+            ("jsweep", "3d_jsweep_tail"),
+            # rows that are no powers of two
+            ("quads", "3d96_5lvl"), ("pairs,quads", "3d96_5lvl"), ("tail", "3d96_5lvl"), ("xzero", "3d96_5lvl"),
+            ("post_noise", "3d96_5lvl"), ("zrestrict", "3d96_5lvl"), (ALL_PATHS, "3d96_5lvl"),
+            ("post_noise", "3d_192x48x48_5lvl"), ("xzero", "3d_192x48x48_5lvl"), ("fuse_prolong", "3d_192x48x48_5lvl"),
+            ("zsweep", "3d_192x48x48_5lvl"), (ALL_PATHS, "3d_192x48x48_5lvl"),
+            ("pairs", "3d_320x24x16"),
+            ("qrestrict", "2d_200x120_4lvl"), ("tail,qrestrict", "2d_200x120_4lvl"), ("rb2d", "2d_200x120_4lvl"),
+            (ALL_PATHS, "2d_200x120_4lvl"),
+            ("qrestrict", "2d_300x200_ssor"), ("quads", "2d_300x200_ssor")]
 
 
 @pytest.mark.parametrize("paths,name", VARIANTS)
@@ -330,6 +368,57 @@ def test_level_kernels_labels(hip_device, name, level, sweep):
     s, p, lat = make(shape, **kw)
     assert s.level_kernels(level)["sweep"].startswith(sweep)
     s.close()
+
+
+# the kernel instances the row length selects (mgmc_capi.hip: quads_lanes, pairs_eligible, qrestrict_threads): the
+# labels the device reports, per level.  A (key, None) entry asserts the key's absence; "sweep^" a prefix.
+ROW_LENGTH_LABELS = [
+    ("3d96_5lvl", 0, {"sweep": "k_sweep_rb<3>", "residual_restrict": "k_zresrestrict<7,64,4>"}),
+    ("3d96_5lvl", 1, {"sweep": "k_sweep_quads<3>", "quads": "window", "noise": "tail"}),
+    ("3d96_5lvl", 2, {"sweep": "k_sweep_quads<3>", "quads": "window", "noise": "tail"}),
+    ("3d96_5lvl", 3, {"sweep": "k_tail<3>"}),
+    ("3d96_5lvl", 4, {"sweep": "k_tail<3>"}),
+    ("3d_192x48x48_5lvl", 0, {"sweep^": "k_zsweep_rb7<"}),
+    ("3d_192x48x48_5lvl", 1, {"quads": "window"}),
+    ("3d_192x48x48_5lvl", 2, {"quads": "window", "noise": "restriction+tail"}),
+    ("3d_320x24x16", 0, {"sweep^": "k_zsweep_rb7<"}),
+    ("3d_320x24x16", 1, {"sweep": "k_sweep_pairs<3>", "quads": None, "residual_restrict": "k_zresrestrict<27,64,4>"}),
+    ("3d136_4lvl", 1, {"quads": "window"}),
+    ("3d136_4lvl", 2, {"quads": "window", "noise": "restriction"}),
+    ("2d_200x120_4lvl", 1, {"residual_restrict": "k_quads_restrict2d"}),
+    ("2d_200x120_4lvl", 2, {"sweep": "k_tail<2>"}),
+    ("2d_200x120_4lvl", 3, {"sweep": "k_tail<2>"}),
+    ("3d128_zsweep", 1, {"quads": None}),  # 32-pair rows: the lane-shift instances
+    ("3d_24x20x12", 0, {"sweep": "k_sweep_rb<3>", "residual_restrict": "k_zresrestrict<7,16,4>"}),
+    ("3d_24x20x12", 1, {"sweep": "k_tail<3>"}),
+    ("3d_24x20x12", 2, {"sweep": "k_tail<3>"}),
+    ("3d_80x48x40_ssor_W", 1, {"sweep": "k_sweep_quads<3>", "quads": "window"}),
+    ("2d_300x200_ssor", 0, {"sweep": "k_rb2d"}),
+    ("2d_300x200_ssor", 1, {"residual_restrict": "k_quads_restrict2d"}),
+    ("2d_100x60", 0, {"sweep": "k_rb2d"}),
+    ("2d_100x60", 1, {"sweep": "k_tail<2>"}),
+    ("2d_100x60", 2, {"sweep": "k_tail<2>"}),
+]
+
+
+def test_row_length_instances(hip_device):
+    """Row length picks the kernel instance: 3D quad-pass rows of npair not dividing 64 run the three-load window
+    (quads=window), 80-pair rows the colour-pair passes, 50-pair 2D rows k_quads_restrict2d, and the levels
+    around them the kernels their CONFIGS comments name."""
+    got = {}
+    for name in dict.fromkeys(n for n, _, _ in ROW_LENGTH_LABELS):
+        shape, kw = CONFIGS[name]
+        s, p, lat = make(shape, **kw)
+        got[name] = [s.level_kernels(level) for level in range(p.nlevel)]
+        print(name, *(";".join(f"{k}={v}" for k, v in d.items()) for d in got[name]), sep="\n  ")
+        s.close()
+    for name, level, want in ROW_LENGTH_LABELS:
+        k = got[name][level]
+        for key, value in want.items():
+            if key.endswith("^"):
+                assert k[key[:-1]].startswith(value), (name, level, k)
+            else:
+                assert k.get(key) == value, (name, level, k)
 
 
 @pytest.mark.parametrize("name,levels", [("2d512_qrestrict", (1, 2)), ("2d_qr_aniso_ssor_W", (1,))])

@@ -98,6 +98,10 @@ SWEEPS = {
     # (every 2D pair-pass level takes the quad passes: the pair passes are what MGMC_DISABLE=quads leaves)
     "pairs2": ((256, 128), dict(nlevel=3), "quads", 1, "k_sweep_pairs<2>"),
     "rb2d": ((256, 256), dict(nlevel=2), None, 0, "k_rb2d"),
+    # 24-pair rows (64 % 24 != 0): the three-load window instances, 120-thread workgroups
+    "quads3_window": ((96, 96, 96), dict(nlevel=5), None, 1, "k_sweep_quads<3>"),
+    # 80-pair rows: the colour-pair passes on their default path, 3 rows = 240 of 256 threads
+    "pairs3_default": ((320, 24, 16), dict(nlevel=3), None, 1, "k_sweep_pairs<3>"),
 }
 
 
@@ -107,6 +111,7 @@ def test_poisoned_noisy_sweep_bitwise(hip_device, monkeypatch, name):
     shape, kw, disable, level, label = SWEEPS[name]
     s, p, lat = make(monkeypatch, shape, disable, **kw)
     assert s.level_kernels(level)["sweep"].startswith(label), s.level_kernels(level)
+    assert s.level_kernels(level).get("quads") == ("window" if name == "quads3_window" else None)
     mc = oracle(p, lat)
     rng = np.random.default_rng(7)
     n = s.level_desc(level)["ndof"]
@@ -222,6 +227,15 @@ CYCLES = {
     # ... so the blocked solves come from test_gpu_cholesky.py's 2d256_nl2 (127^2 > 8,192 coarsest unknowns)
     "2d256_chol_blocked": ((256, 256), dict(nlevel=2, coarse_solver="Cholesky"), None,
                            {1: {"sweep": "k_coarse_chol_blocked"}}),
+    # rows that are no powers of two: the window quad passes reading restriction- and tail-drawn noise under a
+    # three-tile fine z-sweep; k_rb2d with partial tiles over k_quads_restrict2d with idle threads and a tail
+    "3d_192x48x48_5lvl": (*CONFIGS["3d_192x48x48_5lvl"], None,
+                          {0: {"rhs": "zero"}, 1: {"sweep": "k_sweep_quads<3>", "quads": "window"},
+                           2: {"sweep": "k_sweep_quads<3>", "quads": "window", "noise": "restriction+tail"},
+                           3: {"sweep": "k_tail<3>"}, 4: {"sweep": "k_tail<3>"}}),
+    "2d_200x120_4lvl": (*CONFIGS["2d_200x120_4lvl"], None,
+                        {0: {"sweep": "k_rb2d"}, 1: {"residual_restrict": "k_quads_restrict2d"},
+                         2: {"sweep": "k_tail<2>"}, 3: {"sweep": "k_tail<2>"}}),
 }
 
 

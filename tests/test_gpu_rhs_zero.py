@@ -35,6 +35,8 @@ SHAPES = {
     "128x36x24_ssor": ((128, 36, 24), dict(nlevel=2, **SSOR)),
     # the <7,64,4,256> residual + restriction with partial tiles
     "256x40x48": ((256, 40, 48), dict(nlevel=2)),
+    # the zero-f instances above a hierarchy of three-load window quad passes (48- and 24-pair rows) and a tail
+    "192x48x48_5lvl": ((192, 48, 48), dict(nlevel=5)),
 }
 
 

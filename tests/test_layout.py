@@ -39,7 +39,11 @@ def hierarchy(shape, nlevel=12):
 
 
 SHAPES = ([(n, n) for n in range(4, 1030, 6)] + [(n, 2 * n + 4) for n in range(4, 300, 10)] +
-          [(n, n, n) for n in range(4, 300, 4)] + [(132, 36, 20), (260, 68, 8), (512, 16, 24), (68, 132, 260)])
+          [(n, n, n) for n in range(4, 300, 4)] + [(132, 36, 20), (260, 68, 8), (512, 16, 24), (68, 132, 260)] +
+          # the row lengths of tests/test_gpu_parity.py that are no powers of two (96^3 and 136^3 are in the cubes
+          # above): rows of 48 / 24 / 12, 80, 20, 17 pairs below them, odd extents on the coarsest levels
+          [(192, 48, 48), (320, 24, 16), (24, 20, 12), (80, 48, 40), (48, 40, 24), (96, 48, 48),
+           (200, 120), (300, 200), (100, 60)])
 
 
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
