@@ -296,6 +296,30 @@ int mgmc_get_series_chain(mgmc_handle* h, int chain, double* out, size_t n);
 /* HIP stream (hipStream_t) the handle enqueues on */
 int mgmc_get_stream(mgmc_handle* h, void** stream);
 
+/* ---- pointwise field statistics (posterior_statistics, driver_mgmc.cc:118-171) ----
+ * The sample mean and the pointwise variance of the whole field, accumulated on the device: while
+ * enabled, every stride-th cycle of the handle (numbered 1, 2, ... from the enable / reset on; whichever
+ * of mgmc_sample, mgmc_sample_async, mgmc_sample_timed* or mgmc_apply ran it) folds the level-0 state of
+ * every chain, chains in the order 0 .. nchains-1, into one running (mean, M2) pair per vertex with the
+ * Welford update of the QoI moments (mgmc_qoi_moments):
+ *     delta = x - mean;  mean += delta / cnt;  M2 += delta * (x - mean),  cnt = states folded in + 1.
+ * One mean and one M2 field per handle whatever nchains is (the chains sample the same distribution);
+ * the reference's variance E[x^2] - mean^2 is M2 / nrecorded.  The fields stay in HBM (two vectors in the
+ * fine level's padded layout) until mgmc_field_stats_get.  mgmc_set_state, mgmc_set_rhs and
+ * mgmc_set_sample_index do not reset them; mgmc_set_lowrank and mgmc_set_qoi_vector keep them recording.
+ * Disabled (the default) the cycle and its graphs are those of a handle that never enabled them.
+ * MGMC_E_INVALID: a NULL handle, stride < 1, a wrong n, get / reset while disabled; MGMC_E_NOMEM: the
+ * fields could not be allocated (the handle stays disabled and otherwise intact). */
+int mgmc_field_stats_enable(mgmc_handle* h, int stride);  /* stride >= 1; allocates + zeroes, rebuilds graphs;
+                                                             on an enabled handle: reset with the new stride */
+int mgmc_field_stats_disable(mgmc_handle* h);             /* frees, rebuilds graphs; no-op when disabled */
+int mgmc_field_stats_reset(mgmc_handle* h);               /* zero fields and both counters; no graph rebuild */
+int mgmc_field_stats_info(const mgmc_handle* h, int* enabled, int* stride, uint64_t* nrecorded);
+                                                          /* nrecorded = states folded in (recorded cycles x nchains) */
+int mgmc_field_stats_get(mgmc_handle* h, double* mean, double* m2, size_t n);
+                                                          /* reference layout, n = ndof; either pointer may be NULL;
+                                                             waits for the handle's stream */
+
 /* ---- component entry points (host buffers, reference layout) used by the parity tests ---- */
 /* y = Q_level x  (LinearOperator::apply; Q = A + B Sigma^{-1} B^T once mgmc_set_lowrank ran) */
 int mgmc_operator_apply(mgmc_handle* h, int level, const double* x, double* y);

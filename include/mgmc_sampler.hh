@@ -145,6 +145,24 @@ class HipMultigridMCSampler {
     void qoi_moments(int chain, double out[3]) const {
         check(mgmc_qoi_moments_chain(h_.get(), chain, out), h_.get(), "mgmc_qoi_moments_chain");
     }
+    // Pointwise mean / M2 fields accumulated on the device, pooled over the chains (mgmc_field_stats_*;
+    // posterior_statistics, driver_mgmc.cc:118-171): every stride-th cycle from here on is folded in
+    void field_stats(int stride = 1) {
+        check(mgmc_field_stats_enable(h_.get(), stride), h_.get(), "mgmc_field_stats_enable");
+    }
+    void field_stats_off() { check(mgmc_field_stats_disable(h_.get()), h_.get(), "mgmc_field_stats_disable"); }
+    void reset_field_stats() { check(mgmc_field_stats_reset(h_.get()), h_.get(), "mgmc_field_stats_reset"); }
+    // states folded in so far (recorded cycles x nchains); 0 while disabled
+    uint64_t field_stats_recorded() const {
+        uint64_t n = 0;
+        check(mgmc_field_stats_info(h_.get(), nullptr, nullptr, &n), h_.get(), "mgmc_field_stats_info");
+        return n;
+    }
+    // mean and M2 in the reference layout (get_ndof() doubles each; either may be nullptr); the
+    // reference's variance is M2 / field_stats_recorded()
+    void field_moments(double* mean, double* m2) const {
+        check(mgmc_field_stats_get(h_.get(), mean, m2, ndof_), h_.get(), "mgmc_field_stats_get");
+    }
 
    private:
     void adopt(mgmc_handle* h) {

@@ -33,5 +33,6 @@ from .sampler import (  # noqa: F401
     measurement_vector_index,
     sampler_csr_matrix,
 )
+from .vtk import write_vtk, write_vtk_circle  # noqa: F401
 
 __version__ = "0.1.0"

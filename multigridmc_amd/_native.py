@@ -120,6 +120,11 @@ SIGNATURES = [
     ("mgmc_get_series", c_int, [_H, POINTER(c_double), c_size_t]),
     ("mgmc_get_series_chain", c_int, [_H, c_int, POINTER(c_double), c_size_t]),
     ("mgmc_get_stream", c_int, [_H, POINTER(c_void_p)]),
+    ("mgmc_field_stats_enable", c_int, [_H, c_int]),
+    ("mgmc_field_stats_disable", c_int, [_H]),
+    ("mgmc_field_stats_reset", c_int, [_H]),
+    ("mgmc_field_stats_info", c_int, [_H, POINTER(c_int), POINTER(c_int), POINTER(c_uint64)]),
+    ("mgmc_field_stats_get", c_int, [_H, _DP, _DP, c_size_t]),
     ("mgmc_operator_apply", c_int, [_H, c_int, _DP, _DP]),
     ("mgmc_smoother_apply", c_int, [_H, c_int, c_int, c_int, _DP, _DP]),
     ("mgmc_sor_smoother_apply", c_int, [_H, c_int, c_int, c_int, _DP, _DP]),

@@ -1751,7 +1751,17 @@ int build_tails(mgmc_handle* h) {
     if (rc == MGMC_OK) mark_zero_inputs(h);
     if (rc == MGMC_OK) mark_rhs_zero(h);
     if (rc == MGMC_OK) rc = plan_drawn_noise(h);
+    sync_fieldstats_op(h);
     return rc;
+}
+
+// The field-statistics op is the last op of the cycle, after OP_QOI, while the statistics are enabled and
+// absent otherwise: appended once the passes above have run (none of them sees it), so the rest of the
+// op list is what it is without the statistics.  It lies behind seg_end_post: in the timed graph's last
+// (QoI) segment.
+void sync_fieldstats_op(mgmc_handle* h) {
+    while (!h->ops.empty() && h->ops.back().kind == OP_FIELDSTATS) h->ops.pop_back();
+    if (h->fs_mean && !h->ops.empty()) h->ops.push_back({OP_FIELDSTATS, 0, 0, 0, 0});
 }
 
 void enqueue_ops(mgmc_handle* h, size_t begin, size_t end, hipStream_t s) {
@@ -1896,6 +1906,11 @@ void enqueue_ops(mgmc_handle* h, size_t begin, size_t end, hipStream_t s) {
                 hipLaunchKernelGGL(k_qoi_record, dim3(1), dim3(64 * ((nch + 63) / 64)), 0, s,
                                    (const double*)h->levels[0].x, h->ctrl, h->series, h->series_cap, h->mom, nch,
                                    (long long)h->levels[0].L.nstore);
+                break;
+            }
+            case OP_FIELDSTATS: {  // level 0's canonical buffer holds the cycle's state (OP_COPY before OP_QOI)
+                launch_fieldstats(h->levels[0].x, (long long)h->levels[0].L.nstore, nch, h->fs_mean, h->fs_m2,
+                                  h->fs_ctl, s);
                 break;
             }
         }
@@ -2599,6 +2614,9 @@ int mgmc_destroy(mgmc_handle* h) {
     if (h->qv_part) hipFree(h->qv_part);
     if (h->lex_tmp) hipFree(h->lex_tmp);
     if (h->zbuf) hipFree(h->zbuf);
+    if (h->fs_mean) hipFree(h->fs_mean);
+    if (h->fs_m2) hipFree(h->fs_m2);
+    if (h->fs_ctl) hipFree(h->fs_ctl);
     if (h->stream) hipStreamDestroy(h->stream);
     delete h;
     return MGMC_OK;
@@ -3281,6 +3299,103 @@ int mgmc_sample_timed_stride(mgmc_handle* h, int nsteps, int stride, int64_t qoi
     *npost = cpost * nt;
     for (auto& e : ev) hipEventDestroy(e);
     return check_finite(h);
+}
+
+// ---------------- pointwise field statistics (mgmc_fieldstats.hpp; driver_mgmc.cc:118-171) ----------------
+
+// zero both fields and the counters, keep (or set) the stride; on the handle's stream
+static int fieldstats_zero(mgmc_handle* h, int stride) {
+    const size_t bytes = (size_t)h->levels[0].L.nstore * sizeof(double);
+    const uint64_t ctl0[FS_CTL_WORDS] = {0, 0, (uint64_t)stride, 0};
+    HIPCHK(h, hipMemsetAsync(h->fs_mean, 0, bytes, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->fs_m2, 0, bytes, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->fs_ctl, ctl0, sizeof(ctl0), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));  // (ctl0 is on this stack)
+    h->fs_stride = stride;
+    return MGMC_OK;
+}
+
+static void fieldstats_free(mgmc_handle* h) {
+    if (h->fs_mean) hipFree(h->fs_mean);
+    if (h->fs_m2) hipFree(h->fs_m2);
+    if (h->fs_ctl) hipFree(h->fs_ctl);
+    h->fs_mean = h->fs_m2 = nullptr;
+    h->fs_ctl = nullptr;
+    h->fs_stride = 0;
+}
+
+int mgmc_field_stats_enable(mgmc_handle* h, int stride) {
+    if (!h) return fail(nullptr, MGMC_E_INVALID, "null handle");
+    if (stride < 1) return fail(h, MGMC_E_INVALID, "field statistics: stride must be >= 1");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (h->fs_mean) return fieldstats_zero(h, stride);  // enabled: a reset with the new stride (same graphs)
+    const size_t bytes = (size_t)h->levels[0].L.nstore * sizeof(double);
+    if (hipMalloc(&h->fs_mean, bytes) != hipSuccess || hipMalloc(&h->fs_m2, bytes) != hipSuccess ||
+        hipMalloc(&h->fs_ctl, FS_CTL_WORDS * sizeof(uint64_t)) != hipSuccess) {
+        (void)hipGetLastError();
+        fieldstats_free(h);  // disabled, otherwise intact: the op list and the graphs were not touched
+        return fail(h, MGMC_E_NOMEM, "device allocation failed (field statistics)");
+    }
+    int rc = fieldstats_zero(h, stride);
+    if (rc == MGMC_OK) {
+        sync_fieldstats_op(h);
+        rc = build_graphs(h);
+    }
+    if (rc != MGMC_OK) {  // back to the cycle without the op
+        const std::string err = h->last_error;
+        fieldstats_free(h);
+        sync_fieldstats_op(h);
+        (void)build_graphs(h);
+        return fail(h, rc, err);
+    }
+    return MGMC_OK;
+}
+
+int mgmc_field_stats_disable(mgmc_handle* h) {
+    if (!h) return fail(nullptr, MGMC_E_INVALID, "null handle");
+    if (!h->fs_mean) return MGMC_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    destroy_graphs(h);  // they hold the fields' addresses
+    fieldstats_free(h);
+    sync_fieldstats_op(h);
+    return build_graphs(h);
+}
+
+int mgmc_field_stats_reset(mgmc_handle* h) {
+    if (!h) return fail(nullptr, MGMC_E_INVALID, "null handle");
+    if (!h->fs_mean) return fail(h, MGMC_E_INVALID, "field statistics are not enabled (mgmc_field_stats_enable)");
+    HIPCHK(h, hipSetDevice(h->device));
+    return fieldstats_zero(h, h->fs_stride);
+}
+
+int mgmc_field_stats_info(const mgmc_handle* h, int* enabled, int* stride, uint64_t* nrecorded) {
+    if (!h) return fail(nullptr, MGMC_E_INVALID, "null handle");
+    if (enabled) *enabled = h->fs_mean ? 1 : 0;
+    if (stride) *stride = h->fs_stride;
+    if (nrecorded) {
+        *nrecorded = 0;
+        if (h->fs_mean) {
+            if (hipSetDevice(h->device) != hipSuccess ||
+                hipMemcpyAsync(nrecorded, h->fs_ctl + 1, sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+                hipStreamSynchronize(h->stream) != hipSuccess)
+                return fail(nullptr, MGMC_E_HIP, "field statistics: reading the counter failed");
+        }
+    }
+    return MGMC_OK;
+}
+
+int mgmc_field_stats_get(mgmc_handle* h, double* mean, double* m2, size_t n) {
+    if (!h) return fail(nullptr, MGMC_E_INVALID, "null handle");
+    if (!h->fs_mean) return fail(h, MGMC_E_INVALID, "field statistics are not enabled (mgmc_field_stats_enable)");
+    if (n != h->levels[0].spec.ndof) return fail(h, MGMC_E_INVALID, "field statistics size mismatch");
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = MGMC_OK;
+    if (mean && (rc = download(h, 0, h->fs_mean, mean))) return rc;
+    if (m2 && (rc = download(h, 0, h->fs_m2, m2))) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MGMC_OK;
 }
 
 }  // extern "C"

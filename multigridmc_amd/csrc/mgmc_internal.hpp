@@ -45,6 +45,7 @@ static_assert(MGMC_LAYOUT_POINT == mgmc::LF_POINT && MGMC_LAYOUT_PAIRS == mgmc::
 #include "mgmc_field.hpp"
 #include "mgmc_operators.hpp"
 #include "mgmc_rhs_zero.hpp"
+#include "mgmc_fieldstats.hpp"
 
 using namespace mgmc;
 
@@ -62,7 +63,9 @@ enum OpKind {
     OP_COPY = 5,
     OP_COARSE_CHOL = 6,
     OP_TAIL = 7,     // the sub-cycle of the coarsest levels in one workgroup (mgmc_tail.hpp)
-    OP_SWEEP_RESTRICT = 8   // 2D Galerkin level: last pre-sweep + residual + restriction (mgmc_qrestrict.hpp)
+    OP_SWEEP_RESTRICT = 8,  // 2D Galerkin level: last pre-sweep + residual + restriction (mgmc_qrestrict.hpp)
+    OP_FIELDSTATS = 9       // pointwise mean / M2 of the level-0 state (mgmc_fieldstats.hpp); the last op, only
+                            // while mgmc_field_stats_enable holds
 };
 
 struct Op {
@@ -311,6 +314,11 @@ struct mgmc_handle {
     double* qv_part = nullptr;
     long long qv_n = 0;
     int qv_nblk = 0;
+    // pointwise field statistics (mgmc_field_stats_*, mgmc_fieldstats.hpp): enabled <=> fs_mean != nullptr
+    double* fs_mean = nullptr;      // running mean and M2 per stored vertex of level 0, pooled over the chains
+    double* fs_m2 = nullptr;
+    uint64_t* fs_ctl = nullptr;     // [0] cycles seen [1] states recorded [2] stride
+    int fs_stride = 0;
     std::string last_error;
     ncclComm_t comm = nullptr;
     int nranks = 1, rank = 0;
@@ -424,6 +432,7 @@ void launch_coarse_chol(const mgmc_handle* h, const Level& lv, const double* f, 
 Layout tail_layout(const Layout& L);
 void build_ops(mgmc_handle* h);
 int build_tails(mgmc_handle* h);
+void sync_fieldstats_op(mgmc_handle* h);
 bool mark_rhs_zero(mgmc_handle* h);
 int build_graphs(mgmc_handle* h);
 void destroy_graphs(mgmc_handle* h);

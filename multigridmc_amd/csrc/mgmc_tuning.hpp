@@ -70,5 +70,10 @@ constexpr int LR_PART_CH = 1;
 // 16-byte pairs per thread of the dense-column kernels (k_lr_dense_rhs / _update)
 constexpr int LR_DENSE_PER = 8;
 
+// ---- pointwise field statistics (mgmc_fieldstats.hpp) ----
+// threads per workgroup; 16-byte pairs per thread (their loads issued together); one pass per thread
+constexpr int FS_NT = 256;
+constexpr int FS_PAIRS = 1;
+
 }  // namespace tune
 }  // namespace mgmc

@@ -573,6 +573,44 @@ class MultigridMCSampler:
     def reset_moments(self):
         self._chk(self.lib.mgmc_reset_moments(self.handle))
 
+    # -- pointwise field statistics on the device (posterior_statistics, driver_mgmc.cc:118-171) --
+    def field_stats(self, stride: int = 1):
+        """From now on every stride-th cycle (numbered 1, 2, ... from this call), whichever call runs it,
+        folds the state of every chain into one running mean field and one M2 field in HBM
+        (mgmc_field_stats_enable; the Welford update of qoi_moments, chains in order).  On a sampler
+        that already records: a reset with the new stride."""
+        self._chk(self.lib.mgmc_field_stats_enable(self.handle, int(stride)))
+
+    def field_stats_off(self):
+        """Free the fields; the cycle is again the one of a sampler that never recorded them."""
+        self._chk(self.lib.mgmc_field_stats_disable(self.handle))
+
+    def reset_field_stats(self):
+        """Zero the fields, the recorded-state count and the cycle count of the thinning."""
+        self._chk(self.lib.mgmc_field_stats_reset(self.handle))
+
+    def field_stats_info(self) -> dict:
+        """{"enabled": bool, "stride": int (0 while disabled), "nrecorded": states folded in =
+        recorded cycles x nchains}"""
+        en, st, n = ctypes.c_int(), ctypes.c_int(), ctypes.c_uint64()
+        self._chk(self.lib.mgmc_field_stats_info(self.handle, ctypes.byref(en), ctypes.byref(st), ctypes.byref(n)))
+        return {"enabled": bool(en.value), "stride": st.value, "nrecorded": n.value}
+
+    def field_moments(self):
+        """(n, mean, M2): the states folded in, and the mean and the sum of squared deviations per vertex
+        (reference layout, ndof values each)."""
+        mean, m2 = np.empty(self.ndof), np.empty(self.ndof)
+        self._chk(self.lib.mgmc_field_stats_get(self.handle, _dp(mean), _dp(m2), self.ndof))
+        return self.field_stats_info()["nrecorded"], mean, m2
+
+    def field_mean_variance(self):
+        """(mean, M2 / n): the sample mean and the population variance per vertex -- the reference's
+        E[x^2] - mean^2 (driver_mgmc.cc:118-171)."""
+        n, mean, m2 = self.field_moments()
+        if n == 0:
+            raise ValueError("no state has been recorded yet")
+        return mean, m2 / n
+
     def get_series(self, n: int, chain: int = 0) -> np.ndarray:
         """The QoI series of the last sample / sample_async call (waits for this handle's stream)."""
         out = np.empty(max(int(n), 0))
