@@ -179,6 +179,13 @@ int mgmc_stencil_of_csr(const mgmc_config* cfg, int64_t nrow, const int64_t* row
 int mgmc_check_layout(int dim, const int* n, int reach, unsigned families, int zrestrict_cx, int legacy);
 
 /* ---- lifetime ---- */
+/* (seed, chain_id) name the noise stream: every normal is Philox4x32-10 under the 64-bit key
+ * (lo32(seed), lo32(chain_id) ^ hi32(seed)) with the counter (pair id, sweep tag, lo32(sample), hi32(sample)).
+ * The seed and the sample index are full 64-bit words.  The chain id is taken modulo 2^32 in the key, so
+ * every mgmc_create* variant returns MGMC_E_INVALID unless chain_id + nchains - 1 < 2^32 (nchains = 1
+ * here): ids 2^32 apart would draw one stream.  128 bits go into a 64-bit key, so
+ * (seed ^ (d << 32), chain_id ^ d) names the same stream as (seed, chain_id) for every 32-bit d: that
+ * alias is by construction and is not rejected. */
 int mgmc_create(const mgmc_config* cfg, int device, uint64_t seed, uint64_t chain_id, mgmc_handle** out);
 /* A sampler on a fine operator given as a matrix (LinearOperator::A_sparse, linear_operator.hh:187):
  * CSR on cfg's lattice (rows = interior vertices, columns strictly ascending, a positive diagonal,
@@ -191,7 +198,8 @@ int mgmc_create_csr(const mgmc_config* cfg, int64_t nrow, const int64_t* rowptr,
 /* Batched chains (ABI 4): nchains (1..16) independent chains chain0, chain0+1, ... in one handle.
  * They share the hierarchy, the stencils and the low-rank data (B, B_bar); each keeps its own state
  * and right-hand side in HBM and its own Philox key make_key(seed, chain0 + c), so chain c draws
- * exactly what a single-chain handle with chain_id = chain0 + c draws (bitwise).  Every kernel of
+ * exactly what a single-chain handle with chain_id = chain0 + c draws (bitwise); chain0 + nchains - 1
+ * must be below 2^32 (the key's contract, at mgmc_create).  Every kernel of
  * the cycle covers all chains in one launch; the low-rank fix reads B_bar once per row for all
  * chains (x -= B_bar W, W = B^T X: the (N x m)(m x C) product of the batch, sor_smoother.cc:47-51).
  * The entry points below without _chain act on every chain (set_rhs, set_state: the same vector)

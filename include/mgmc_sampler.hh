@@ -75,7 +75,8 @@ inline mgmc_config make_config(int dim, int nx, int ny, int nz, double kappa_sq,
 class HipMultigridMCSampler {
    public:
     // nchains > 1: a batch of chains chain_id .. chain_id + nchains - 1 in one handle
-    // (mgmc_create_batch); apply / set_state act on every chain, the *_chain accessors on one
+    // (mgmc_create_batch); apply / set_state act on every chain, the *_chain accessors on one.
+    // chain_id + nchains - 1 must be below 2^32 (the Philox key's contract, mgmc.h): the C-ABI's error is thrown
     HipMultigridMCSampler(const mgmc_config& cfg, int device, uint64_t seed, uint64_t chain_id = 0, int nchains = 1) {
         mgmc_handle* h = nullptr;
         check(mgmc_create_batch(&cfg, device, seed, chain_id, nchains, &h), nullptr, "mgmc_create");

@@ -2240,6 +2240,10 @@ static int create_impl(const mgmc_config* cfg, const CsrHost* csr, int device, u
     *out = nullptr;
     if (nchains < 1 || nchains > LR_MAX_CH)
         return fail(nullptr, MGMC_E_INVALID, "nchains must be in [1, " + std::to_string(LR_MAX_CH) + "]");
+    // make_key takes lo32(chain): ids 2^32 apart would draw one stream (nchains <= LR_MAX_CH: no overflow)
+    if (chain_id > 0xffffffffull || chain_id + (uint64_t)(nchains - 1) > 0xffffffffull)
+        return fail(nullptr, MGMC_E_INVALID,
+                    "chain ids are taken modulo 2^32 in the Philox key: chain_id + nchains - 1 must be below 2^32");
     const std::string err = validate_config(*cfg);
     if (!err.empty()) return fail(nullptr, MGMC_E_INVALID, err);
     std::vector<CsrHost> mats;  // per level (matrix path)

@@ -224,6 +224,10 @@ class Oracle:
     def set_sample_index(self, index):
         self.L.orc_set_sample_index(self.h, int(index))
 
+    def reseed(self, seed, chain):
+        """orc_reseed: the Philox key's (seed, chain) of a MULTICOLOUR oracle (FAITHFUL: mt19937_64(seed + chain))."""
+        self.L.orc_reseed(self.h, int(seed), int(chain))
+
     def get_state(self):
         x = np.empty(self.ndof())
         self.L.orc_get_state(self.h, dp(x))

@@ -29,23 +29,25 @@ POSTERIOR = ["2d32_point_global", "3d32_ball_global", "3d128_zsweep_points", "3d
              "3d128_global_inplace_W"]
 
 
-def _prior(name, nchains=1, chain=0):
+def _prior(name, nchains=1, chain=0, seed=SEED):
     shape, kw = PAR.CONFIGS[name]
     p = mg.MultigridParameters(**{"nlevel": 3, "smoother": "SOR", "coarse_solver": "SSOR", **kw})
     lat = mg.Lattice(*shape)
     op = mg.ShiftedLaplaceFDOperator(lat, 25.0)
-    return mg.MultigridMCSampler(op, SEED, p, device=0, chain_id=chain, nchains=nchains), lat
+    return mg.MultigridMCSampler(op, seed, p, device=0, chain_id=chain, nchains=nchains), lat
 
 
-def _posterior(name, nchains=1, chain=0):
+def _posterior(name, nchains=1, chain=0, seed=SEED):
     shape, kw, (radius, nmeas, glob) = LR.CONFIGS[name]
     p = mg.MultigridParameters(**{"nlevel": 3, "smoother": "SOR", "coarse_solver": "SSOR", **kw})
     op, lat = LR.measured(shape, 25.0, radius, nmeas, glob)
-    return mg.MultigridMCSampler(op, SEED, p, device=0, chain_id=chain, nchains=nchains), lat
+    return mg.MultigridMCSampler(op, seed, p, device=0, chain_id=chain, nchains=nchains), lat
 
 
-def _check_batch(make, name, nchains=3, nsteps=5):
-    b, lat = make(name, nchains=nchains, chain=CHAIN0)
+def _check_batch(make, name, nchains=3, nsteps=5, seed=SEED, chain0=CHAIN0, sample0=None):
+    """sample0: the sample index set on the batch and on every one-chain handle before sampling (None: as created).
+    Returns the batch's series with the inputs (zb, f, x0, qoi), for a comparison with the oracle."""
+    b, lat = make(name, nchains=nchains, chain=chain0, seed=seed)
     assert b.nchains == nchains and b.lib.mgmc_nchains(b.handle) == nchains
     rng = np.random.default_rng(17)
     f = rng.standard_normal(lat.Nvertex)
@@ -53,11 +55,15 @@ def _check_batch(make, name, nchains=3, nsteps=5):
     qoi = mg.measurement_vector_index(lat, [0.5] * lat.dim)
     b.fix_rhs(f)
     b.set_state(x0)
+    if sample0 is not None:
+        b.set_sample_index(sample0)
     zb = b.sample(nsteps, qoi, chain=None)
     for c in range(nchains):
-        s, _ = make(name, chain=CHAIN0 + c)
+        s, _ = make(name, chain=chain0 + c, seed=seed)
         s.fix_rhs(f)
         s.set_state(x0)
+        if sample0 is not None:
+            s.set_sample_index(sample0)
         z = s.sample(nsteps, qoi)
         assert np.all(np.isfinite(z))
         assert np.array_equal(zb[c], z), f"chain {c}: QoI series"
@@ -67,6 +73,7 @@ def _check_batch(make, name, nchains=3, nsteps=5):
     # chains with different ids differ
     assert not np.array_equal(zb[0], zb[1])
     b.close()
+    return zb, f, x0, qoi
 
 
 @pytest.mark.parametrize("name", PRIOR)

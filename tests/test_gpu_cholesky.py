@@ -29,16 +29,16 @@ CONFIGS = {
 }
 
 
-def _make(shape, kw, kappa_sq=25.0, chain=0, nchains=1):
+def _make(shape, kw, kappa_sq=25.0, chain=0, nchains=1, seed=SEED):
     p = mg.MultigridParameters(**{"nlevel": 2, "smoother": "SOR", "coarse_solver": "Cholesky", **kw})
     lat = mg.Lattice(*shape)
-    s = mg.MultigridMCSampler(mg.ShiftedLaplaceFDOperator(lat, kappa_sq), SEED, p, device=0, chain_id=chain,
+    s = mg.MultigridMCSampler(mg.ShiftedLaplaceFDOperator(lat, kappa_sq), seed, p, device=0, chain_id=chain,
                               nchains=nchains)
     return s, p, lat
 
 
-def _oracle(s, p, lat, kappa_sq=25.0, chain=0):
-    return O.Oracle.fd_own(lat.shape, p, kappa_sq, mode=O.MULTICOLOUR, seed=SEED, chain=chain)
+def _oracle(s, p, lat, kappa_sq=25.0, chain=0, seed=SEED):
+    return O.Oracle.fd_own(lat.shape, p, kappa_sq, mode=O.MULTICOLOUR, seed=seed, chain=chain)
 
 
 @pytest.mark.parametrize("name", list(CONFIGS))

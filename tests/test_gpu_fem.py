@@ -31,12 +31,12 @@ CONFIGS = {
 }
 
 
-def make(name, kappa_sq=25.0, chain=0):
+def make(name, kappa_sq=25.0, chain=0, seed=SEED):
     shape, kw = CONFIGS[name]
     p = mg.MultigridParameters(**{"nlevel": 3, "smoother": "SOR", "coarse_solver": "SSOR", **kw})
     lat = mg.Lattice(*shape)
-    s = mg.MultigridMCSampler(mg.ShiftedLaplaceFEMOperator(lat, kappa_sq), SEED, p, device=0, chain_id=chain)
-    mc = O.Oracle.fem(shape, p, kappa_sq, mode=O.MULTICOLOUR, seed=SEED, chain=chain)
+    s = mg.MultigridMCSampler(mg.ShiftedLaplaceFEMOperator(lat, kappa_sq), seed, p, device=0, chain_id=chain)
+    mc = O.Oracle.fem(shape, p, kappa_sq, mode=O.MULTICOLOUR, seed=seed, chain=chain)
     return s, mc, p, lat
 
 

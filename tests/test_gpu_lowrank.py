@@ -56,12 +56,12 @@ def measured(shape, kappa_sq, radius, nmeas, glob, seed=1212417, scale=1e-3):
     return mg.MeasuredOperator(mg.ShiftedLaplaceFDOperator(lat, kappa_sq), mp), lat
 
 
-def make(name, kappa_sq=25.0, chain=0):
+def make(name, kappa_sq=25.0, chain=0, seed=SEED):
     shape, kw, (radius, nmeas, glob) = CONFIGS[name]
     p = mg.MultigridParameters(**{"nlevel": 3, "smoother": "SOR", "coarse_solver": "SSOR", **kw})
     op, lat = measured(shape, kappa_sq, radius, nmeas, glob)
-    s = mg.MultigridMCSampler(op, SEED, p, device=0, chain_id=chain)
-    mc = O.Oracle.fd_own(lat.shape, p, kappa_sq, mode=O.MULTICOLOUR, seed=SEED, chain=chain)
+    s = mg.MultigridMCSampler(op, seed, p, device=0, chain_id=chain)
+    mc = O.Oracle.fd_own(lat.shape, p, kappa_sq, mode=O.MULTICOLOUR, seed=seed, chain=chain)
     mc.set_lowrank(op.get_B())
     return s, mc, p, lat, op
 

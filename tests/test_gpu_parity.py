@@ -25,16 +25,16 @@ pytestmark = pytest.mark.gpu
 SEED = 5418513
 
 
-def make(shape, kappa_sq=25.0, chain=0, **kw):
+def make(shape, kappa_sq=25.0, chain=0, seed=SEED, **kw):
     p = mg.MultigridParameters(**{"nlevel": 3, "smoother": "SOR", "coarse_solver": "SSOR", **kw})
     lat = mg.Lattice(*shape)
-    s = mg.MultigridMCSampler(mg.ShiftedLaplaceFDOperator(lat, kappa_sq), SEED, p, device=0, chain_id=chain)
+    s = mg.MultigridMCSampler(mg.ShiftedLaplaceFDOperator(lat, kappa_sq), seed, p, device=0, chain_id=chain)
     return s, p, lat
 
 
-def oracle_for(sampler, p, lat, kappa_sq=25.0, mode=O.MULTICOLOUR, chain=0):
+def oracle_for(sampler, p, lat, kappa_sq=25.0, mode=O.MULTICOLOUR, chain=0, seed=SEED):
     """The oracle with its own Galerkin hierarchy (no device stencil fed in)."""
-    return O.Oracle.fd_own(lat.shape, p, kappa_sq, mode=mode, seed=SEED, chain=chain)
+    return O.Oracle.fd_own(lat.shape, p, kappa_sq, mode=mode, seed=seed, chain=chain)
 
 
 CONFIGS = {
@@ -46,6 +46,11 @@ CONFIGS = {
     "3d64_4lvl": ((64, 64, 64), dict(nlevel=4, omega=1.2)),
     "2d16_1lvl": ((16, 16), dict(nlevel=1, ncoarsesmooth=2)),
     "3d8_1lvl": ((8, 8, 8), dict(nlevel=1)),
+    # k_coarse_ssor_lds with more than 4 x 1024 pair items (sweeps x rows x pairs: 4 x 47 x 24 = 4512 and
+    # 6 x 121 x 6 = 4356) whose right-hand sides still fit LDS: the items past the first four per thread are drawn
+    # in the kernel's second loop
+    "2d48_1lvl_items": ((48, 48), dict(nlevel=1, ncoarsesmooth=2)),
+    "3d12_1lvl_items": ((12, 12, 12), dict(nlevel=1, ncoarsesmooth=3)),
     "2d256_global_coarse": ((256, 256), dict(nlevel=2)),
     "3d32_W_ssor": ((32, 32, 32), dict(nlevel=3, cycle=2, smoother="SSOR")),
     # fused z-marching fine sweep (nx % 128 == 0): ping-pong buffers, prolongation fused into the

@@ -37,7 +37,7 @@ OPS = {"fd": mg.ShiftedLaplaceFDOperator, "fem": mg.ShiftedLaplaceFEMOperator,
        "squared": mg.SquaredShiftedLaplaceFDOperator}
 
 
-def make(name, lowrank=False, chain=0):
+def make(name, lowrank=False, chain=0, seed=SEED):
     shape, pde, model, kw = CONFIGS[name]
     p = mg.MultigridParameters(**{"nlevel": 3, "smoother": "SOR", "coarse_solver": "SSOR", **kw})
     lat = mg.Lattice(*shape)
@@ -48,10 +48,12 @@ def make(name, lowrank=False, chain=0):
         mp.measurement_locations = [list(rng.uniform(0.15, 0.85, lat.dim)) for _ in range(3)]
         mp.variance = list(1.0 + 2.0 * rng.random(3))
         op = mg.MeasuredOperator(op, mp)
-    s = mg.MultigridMCSampler(op, SEED, p, device=0, chain_id=chain)
+    s = mg.MultigridMCSampler(op, seed, p, device=0, chain_id=chain)
     base = getattr(op, "base_operator", op)
     rowptr, col, val = base.get_csr()
-    mc = O.Oracle.csr(shape, p, rowptr, col, val, mode=O.MULTICOLOUR, seed=SEED)
+    mc = O.Oracle.csr(shape, p, rowptr, col, val, mode=O.MULTICOLOUR, seed=seed)
+    if chain:  # orc_create_csr takes no chain id: set the Philox key's chain word afterwards
+        mc.reseed(seed, chain)
     if lowrank:
         mc.set_lowrank(op.get_B())
     return s, mc, p, lat

@@ -83,6 +83,45 @@ def test_create_without_gpu_fails_loudly():
         mg.MultigridMCSampler(mg.ShiftedLaplaceFDOperator(lat, 25.0), 1, mg.MultigridParameters(nlevel=2))
 
 
+def _create(chain_id, nchains=None):
+    """(return code, error text) of mgmc_create (nchains None) / mgmc_create_batch on a tiny 3D configuration."""
+    lib = mg.load_library()
+    c = _cfg((8, 8, 8), nlevel=2)
+    h = ctypes.c_void_p()
+    if nchains is None:
+        rc = lib.mgmc_create(ctypes.byref(c), 0, 0x9E3779B97F4A7C15, chain_id, ctypes.byref(h))
+    else:
+        rc = lib.mgmc_create_batch(ctypes.byref(c), 0, 0x9E3779B97F4A7C15, chain_id, nchains, ctypes.byref(h))
+    msg = _native.last_error(None)
+    if rc == _native.MGMC_OK:
+        lib.mgmc_destroy(h)
+    return rc, msg
+
+
+@pytest.mark.parametrize("chain_id,nchains", [(2 ** 32, None), (2 ** 32, 1), (2 ** 32, 4), (2 ** 32 - 2, 4),
+                                              (2 ** 33 - 4, None), (2 ** 64 - 1, 2)])
+def test_create_rejects_chain_ids_that_alias_in_the_philox_key(chain_id, nchains):
+    """The key takes lo32(chain): ids 2^32 apart would draw one stream, so chain_id + nchains - 1 must stay
+    below 2^32 -- MGMC_E_INVALID before any device call, on any host, with the reason."""
+    rc, msg = _create(chain_id, nchains)
+    assert rc == _native.MGMC_E_INVALID
+    assert "modulo 2^32" in msg and "Philox key" in msg
+
+
+@pytest.mark.parametrize("chain_id,nchains", [(2 ** 32 - 4, 4), (2 ** 32 - 1, None), (2 ** 32 - 1, 1)])
+def test_create_accepts_the_largest_chain_ids(chain_id, nchains):
+    """chain_id + nchains - 1 = 2^32 - 1 is valid: without a HIP device the call gets as far as "no HIP device"
+    (MGMC_E_HIP, as test_create_without_gpu_fails_loudly shows for valid input), with one it succeeds."""
+    hip = ctypes.CDLL("libamdhip64.so")
+    n = ctypes.c_int(0)
+    have_gpu = hip.hipGetDeviceCount(ctypes.byref(n)) == 0 and n.value > 0
+    rc, msg = _create(chain_id, nchains)
+    if have_gpu:
+        assert rc == _native.MGMC_OK, msg
+    else:
+        assert rc == _native.MGMC_E_HIP and "no HIP device" in msg
+
+
 def test_unknown_disable_token_rejected_before_any_device_call(monkeypatch):
     """MGMC_DISABLE (the kernel-path switches, mgmc_capi.hip PathFlag) is parsed before the device is
     touched; an unknown token is MGMC_E_INVALID with its name, on any host."""

@@ -81,6 +81,20 @@ def test_philox_normals_distribution():
     assert abs(np.corrcoef(z[:2000], z2)[0, 1]) < 0.1 and abs(np.corrcoef(z[:2000], z3)[0, 1]) < 0.1
 
 
+def test_philox_key_uses_high_seed_and_sample_words():
+    """The key is (lo32(seed), lo32(chain) ^ hi32(seed)) and the counter carries hi32(sample) (philox_normal.h,
+    DESIGN.md section 4): clearing hi32(seed) or adding 2^32 to the sample index names another, uncorrelated
+    stream (|corr| < 5 / sqrt(n), n = 200000: 5 sigma of a sample correlation of independent normals), and
+    (seed ^ (d << 32), chain ^ d) names the same stream bit for bit -- the alias the contract documents."""
+    seed, c, n = 0x9E3779B97F4A7C15, 2 ** 32 - 5, 200000
+    z = O.philox_normals(seed, c, 0, n, 7, 11)
+    for other in (O.philox_normals(seed & 0xffffffff, c, 0, n, 7, 11), O.philox_normals(seed, c, 0, n, 7, 11 + 2 ** 32)):
+        assert not np.array_equal(z, other)
+        assert abs(np.corrcoef(z, other)[0, 1]) < 5 / np.sqrt(n)
+    d = 0x5A5A0F0F
+    assert np.array_equal(z, O.philox_normals(seed ^ (d << 32), c ^ d, 0, n, 7, 11))
+
+
 def test_oracle_math_accuracy():
     import ctypes
     import math
