@@ -264,24 +264,6 @@ void launch_zsweep(const Level& lv, const double* xin, double* xout, const doubl
     launch_zsweep_t<ZS_XP, ZS_TY, ZS_NT, ZS_MINW>(lv, a, false, s, nch, fzero);
 }
 
-// colour-pair passes of a Galerkin 9/27-point level (in place): forward colours (0,1), (2,3), ...,
-// backward (7,6), (5,4), ... -- 2^(d-1) passes per sweep
-bool pairs_eligible(const LevelSpec& sp, const Layout& L) {
-    return (sp.npoints == 27 || sp.npoints == 9) && L.nx / 2 >= 1 && L.nx / 2 <= 256 && L.nx % 2 == 0;
-}
-
-// both colour pairs of a k-parity half per launch (k_sweep_quads): on levels with rows of <= 64
-// pairs, where each pair pass is launch-latency bound and halving the launches pays (256^3: 63^3
-// level 4 x 5.0 -> 2 x 7.6 us, 31^3 level 4 x 4.8 -> 2 x 6.3 us per sweep; round 4, 127^3 level with
-// the folded stencil and xzero: 8 x 8 -> 61 us per cycle, 256^3 cycle -8 us), and on every 2D pair-pass
-// level (2D 1024^2 FD cycle 0.135 -> 0.129 ms, FEM 0.147 -> 0.139 ms; A/B in one box call).  On the
-// large 3D levels it loses (512^3 level 1: 2 x 105 us against 4 x 41 us per sweep): the
-// second pair's loads wait for the first pair's rows.  Levels that k_tail runs are left to it (caller).
-bool quads_eligible(const LevelSpec& sp, const Layout& L, uint32_t paths) {
-    if (!pairs_eligible(sp, L) || (paths & PATH_NO_QUADS)) return false;
-    return sp.dim == 2 || L.nx / 2 <= tune::QUADS_MAXPAIR;
-}
-
 // one red-black sweep of a 2D 5-point level, xin -> xout (mgmc_rb2d.hpp)
 void launch_rb2d(const Level& lv, const double* xin, double* xout, const double* f, const GibbsArg& g, int direction,
                  bool noise, hipStream_t s, int nch = 1) {
@@ -294,19 +276,6 @@ void launch_rb2d(const Level& lv, const double* xin, double* xout, const double*
     else
         hipLaunchKernelGGL((k_rb2d<false>), grid, block, 0, s, lv.L, xin, xout, f, lv.S, g, c1, ntx, cs);
 }
-
-// j-marching half-sweeps (k_jsweep_half): 3D 27-point levels with rows of 128 or 256 pairs (nx = 256: level 1
-// at 512^3; nx = 512: the FEM prior's fine level at 512^3), x read about 1.5 times per half instead of once
-// per colour-pair pass (DESIGN.md sections 3a, 3c; 512^3 FEM cycle 4.65 -> 3.76 ms).
-// With 64-pair rows (512^3 level 2, 256^3 level 1) the kernel is slower than the pair passes (2 x 21 against
-// 4 x 8 us per sweep at 127^3, 256^3 cycle 0.484 -> 0.503 ms): those levels are latency-bound, and the
-// march's chunks are short.
-bool jsweep_eligible(const LevelSpec& sp, const Layout& L, uint32_t paths) {
-    return sp.dim == 3 && sp.npoints == 27 && (L.nx == 256 || L.nx == 512) &&
-           L.ny >= 2 && L.nz >= 2 &&
-           !(paths & PATH_NO_JSWEEP);
-}
-
 
 // xzero: xin is known zero (Op::xzero): the first half takes zeros for every x row, the second for its own
 // planes (the neighbouring planes are the first half's new values)
@@ -359,19 +328,10 @@ void launch_jsweep(const Level& lv, const double* xin, double* xout, const doubl
     }
 }
 
-// 3D quad-pass rows of npair dividing 64 (127^3 / 63^3 / 31^3 ...): whole rows per wavefront, the window's outer
-// columns by lane shifts (k_sweep_quads LANES); every other row length takes the three-load window
-// (mgmc_level_kernels: quads=window)
-bool quads_lanes(int dim, int npair) { return dim == 3 && 64 % npair == 0 && tune::QUADS_LANES != 0; }
-
 // zb: the sweep's Box-Muller pairs, drawn by an earlier launch (Op::pnz, plan_drawn_noise; 3D quad-pass
 // levels, one chain; with xzero forward sweeps only)
 void launch_quads(const Level& lv, const double* xin, double* xout, const double* f, const GibbsArg& g, int direction,
                   hipStream_t s, int nch = 1, bool xzero = false, const double2* zb = nullptr) {
-    if (lv.jsweep) {
-        launch_jsweep(lv, xin, xout, f, g, direction, s, nch, xzero);
-        return;
-    }
     QuadPassArgs a;
     a.zb = zb;
     a.cs = lv.L.nstore;
@@ -404,7 +364,7 @@ void launch_quads(const Level& lv, const double* xin, double* xout, const double
         const dim3 grid(a.nblk_y * nk, 1, nch);
         if (dim == 3) {
             // xzero (3D): the first half takes every x row as 0.0, the second its own planes' rows
-            // lanes: quads_lanes above
+            // lanes: quads_lanes (mgmc_level_plan.hpp)
 #define MGMC_QD_LAUNCH(SYMV, XZ)                                                                            \
     do {                                                                                                    \
         if (lanes) {                                                                                        \
@@ -481,6 +441,44 @@ void launch_pairs(const Level& lv, double* x, const double* f, const GibbsArg& g
             else hipLaunchKernelGGL((k_sweep_pairs<2, false>), grid, dim3(nt), 0, s, a);
         }
     }
+}
+
+// One noisy sweep of lv, by the kernel lv.sweep names: the cycle's (enqueue_ops) and the per-level entry
+// points' (sweep_component).  The out-of-place kernels read xin and write xout, the others sweep xin in
+// place; returns the buffer that holds the result.  Noise-free sweeps go to launch_sweep.
+struct SweepOpts {
+    const Level* coarse = nullptr;  // ZSWEEP: fused prolongate-add of alpha P xc (the coarser level's x)
+    const double* xc = nullptr;
+    double alpha = 0.0;
+    const LRRhsArg* lrr = nullptr;  // ZSWEEP: the right-hand side is read in place (LowRankDev::rhs_inplace)
+    bool fzero = false;             // ZSWEEP: f is known to be all +0.0 (Op::fzero)
+    bool xzero = false;             // QUADS (3D) / JSWEEP: xin is known zero (Op::xzero)
+    const double2* zb = nullptr;    // QUADS (3D): the sweep's Box-Muller pairs, drawn by an earlier launch (Op::pnz)
+};
+double* launch_level_sweep(const Level& lv, double* xin, double* xout, const double* f, const GibbsArg& g,
+                           int direction, hipStream_t s, int nch = 1, const SweepOpts& o = SweepOpts()) {
+    switch (lv.sweep) {
+        case SweepKernel::ZSWEEP:
+            launch_zsweep(lv, xin, xout, f, g, direction, o.coarse, o.xc, o.alpha, s, nch, o.lrr, o.fzero);
+            return xout;
+        case SweepKernel::JSWEEP:
+            launch_jsweep(lv, xin, xout, f, g, direction, s, nch, o.xzero);
+            return xout;
+        case SweepKernel::QUADS:
+            launch_quads(lv, xin, xout, f, g, direction, s, nch, o.xzero, o.zb);
+            return xout;
+        case SweepKernel::RB2D:
+            launch_rb2d(lv, xin, xout, f, g, direction, true, s, nch);
+            return xout;
+        case SweepKernel::PAIRS:
+            launch_pairs(lv, xin, f, g, direction, s, nch);
+            return xin;
+        case SweepKernel::FIELD:
+        case SweepKernel::COLOUR:
+            launch_sweep(lv, xin, f, g, direction, true, s, nch);
+            return xin;
+    }
+    return xin;
 }
 
 // the coarse SSOR sampler's right-hand sides are precomputed when they fit next to x and f
@@ -598,95 +596,79 @@ void launch_zresrestrict_t(const Level& lf, const Level& lc, const double* x, co
                        zrestrict_lds_bytes(CX, CY), s, a);
 }
 
-// tn: the small z-marching kernel also draws a tail's noise (zr_small_path; ignored elsewhere)
+// The residual + restriction from lf onto lc, as lf.res says (mgmc_level_plan.hpp plan_residual); x_c is zeroed.
+// tn: the small z-marching kernel also draws a tail's noise (ResidualPlan::tail_noise; ignored elsewhere)
 // skip_xc: the z-marching kernel leaves x_c alone (Op::xzero: the coarse level's first sweep takes it as
 // zeros without loading it)
-// the levels whose residual + restriction runs a k_zresrestrict instance with an LRF variant (the
-// 7-point z-marching kernels of the non-small coarse levels: launch_residual_restrict below)
-bool zres_lrf_capable(const Level& lf, const Level& lc) {
-    return lf.spec.dim == 3 && lf.spec.npoints == 7 && !lf.field && !(lf.paths & PATH_NO_ZRESTRICT) &&
-           lc.L.nx >= 8 && lc.L.nx >= tune::ZR_SMALL_NX;
-}
-
-// lr (non-null): the level's right-hand side is read in place (LRRhsArg; zres_lrf_capable levels only)
-// the z-marching 27-point residual + restriction of a non-small coarse level: launch_residual_restrict's path
-// for zero_xc = 1 that can also draw the coarse level's first pre-sweep's noise (pn)
-bool zres_draws_noise(const Level& lf, const Level& lc) {
-    return lf.spec.dim == 3 && lf.spec.npoints == 27 && !lf.field && !(lf.paths & PATH_NO_ZRESTRICT) &&
-           lc.L.nx >= tune::ZR_SMALL_NX;
-}
-
+// lr (non-null): the level's right-hand side is read in place (LRRhsArg; ResidualPlan::lrf levels only)
+// pn: the 27-point z-marching kernel of a non-small coarse level also draws the coarse level's first
+// pre-sweep's noise (ResidualPlan::pre_noise; ignored elsewhere)
+// fzero: f is known to be all +0.0 (Op::fzero, rhs_zero_residual_ok: ResidualPlan::fz levels only)
 void launch_residual_restrict(const Level& lf, const Level& lc, const double* x, const double* f, double* fc,
-                              double* xc, int zero_xc, hipStream_t s, int nch, const TailNoiseLaunch* tn,
-                              bool skip_xc, const LRRhsArg* lr, const PreNoiseLaunch* pn, bool fzero) {
-    const bool zr = lf.spec.dim == 3 && zero_xc && !lf.field && !(lf.paths & PATH_NO_ZRESTRICT) && lc.L.nx >= 8;
-    if (nch > 1 && !zr) {  // batched chains on the generic kernels: one launch per chain
+                              double* xc, hipStream_t s, int nch, const TailNoiseLaunch* tn, bool skip_xc,
+                              const LRRhsArg* lr, const PreNoiseLaunch* pn, bool fzero) {
+    const ResidualPlan& p = lf.res;
+    if (nch > 1 && p.kind != ResidualKind::ZMARCH) {  // batched chains on the generic kernels: one launch per chain
         for (int c = 0; c < nch; ++c)
             launch_residual_restrict(lf, lc, chain_ptr(x, lf, c), chain_ptr(f, lf, c), chain_ptr(fc, lc, c),
-                                     chain_ptr(xc, lc, c), zero_xc, s, 1);
+                                     chain_ptr(xc, lc, c), s, 1);
         return;
     }
-    if (lf.field) {  // r = f - A x into the level's scratch, then fc = R r (and x_c = 0)
-        dim3 block(64, 4, 1);
-        dim3 grid = grid3(lf.L.nx - 1, lf.L.ny - 1, lf.spec.dim == 3 ? lf.L.nz - 1 : 1, block);
-        dim3 gc = grid3(lc.L.nx - 1, lc.L.ny - 1, lf.spec.dim == 3 ? lc.L.nz - 1 : 1, block);
-        if (lf.spec.dim == 3) {
-            hipLaunchKernelGGL((k_fresidual<3>), grid, block, 0, s, lf.L, x, f, lf.F, lf.rbuf);
-            hipLaunchKernelGGL((k_restrict<3>), gc, block, 0, s, lf.L, lc.L, (const double*)lf.rbuf, fc);
-        } else {
-            hipLaunchKernelGGL((k_fresidual<2>), grid, block, 0, s, lf.L, x, f, lf.F, lf.rbuf);
-            hipLaunchKernelGGL((k_restrict<2>), gc, block, 0, s, lf.L, lc.L, (const double*)lf.rbuf, fc);
+    const int dim = lf.spec.dim;
+    const dim3 block(64, 4, 1);
+    const dim3 gc = grid3(lc.L.nx - 1, lc.L.ny - 1, dim == 3 ? lc.L.nz - 1 : 1, block);
+    switch (p.kind) {
+        case ResidualKind::NONE: break;  // (check_level: never called on the coarsest level)
+        case ResidualKind::FIELD: {  // r = f - A x into the level's scratch, then fc = R r (and x_c = 0)
+            const dim3 grid = grid3(lf.L.nx - 1, lf.L.ny - 1, dim == 3 ? lf.L.nz - 1 : 1, block);
+            if (dim == 3) {
+                hipLaunchKernelGGL((k_fresidual<3>), grid, block, 0, s, lf.L, x, f, lf.F, lf.rbuf);
+                hipLaunchKernelGGL((k_restrict<3>), gc, block, 0, s, lf.L, lc.L, (const double*)lf.rbuf, fc);
+            } else {
+                hipLaunchKernelGGL((k_fresidual<2>), grid, block, 0, s, lf.L, x, f, lf.F, lf.rbuf);
+                hipLaunchKernelGGL((k_restrict<2>), gc, block, 0, s, lf.L, lc.L, (const double*)lf.rbuf, fc);
+            }
+            hipMemsetAsync(xc, 0, lc.L.nstore * sizeof(double), s);
+            break;
         }
-        if (zero_xc) hipMemsetAsync(xc, 0, lc.L.nstore * sizeof(double), s);
-        return;
-    }
-    // z-marching kernel on every 3D level with coarse n >= 8: 64 x 4 coarse points per workgroup from
-    // coarse n = ZR_SMALL_NX up, 16 x 4 points (one wavefront) below, where the wide tiles would leave
-    // most of the chip idle (the 27-point gather kernel took 24 us per launch on the 15^3 / 7^3 levels)
-    if (lf.spec.dim == 3 && zero_xc && !(lf.paths & PATH_NO_ZRESTRICT) && lc.L.nx >= 8) {
-        const bool small = lc.L.nx < tune::ZR_SMALL_NX;
-        if (skip_xc) xc = nullptr;
-        if (lr) {  // (zres_lrf_capable)
-            if ((long long)((lc.L.nx + 62) / 64) * ((lc.L.ny + 6) / 8) * (lc.L.nz - 1) >= tune::ZR7_WIDE_MIN_TILES)
-                launch_zresrestrict_t<7, 64, 8, 512, false, true>(lf, lc, x, f, fc, xc, s, nch, nullptr, lr);
-            else launch_zresrestrict_t<7, 64, 4, 256, false, true>(lf, lc, x, f, fc, xc, s, nch, nullptr, lr);
-        } else if (lf.spec.npoints == 7 && fzero && !small) {
-            // f known to be all +0.0 (Op::fzero, rhs_zero_residual_ok: never the small kernel): the FZ instances
-            if ((long long)((lc.L.nx + 62) / 64) * ((lc.L.ny + 6) / 8) * (lc.L.nz - 1) >= tune::ZR7_WIDE_MIN_TILES)
-                launch_zresrestrict_t<7, 64, 8, 512, false, false, true>(lf, lc, x, f, fc, xc, s, nch);
-            else launch_zresrestrict_t<7, 64, 4, 256, false, false, true>(lf, lc, x, f, fc, xc, s, nch);
-        } else if (lf.spec.npoints == 7) {
-            if (small) launch_zresrestrict_t<7, 16, 4, 64>(lf, lc, x, f, fc, xc, s, nch, tn);
-            // 64 x 8 coarse points, 512 threads, 80 KB of LDS (2 workgroups per CU): half the y halo
-            // of 64 x 4 (19 x planes rows per 16 fine rows instead of 11 per 8); 512^3 with kz 32:
-            // 505-525 -> 488-502 us (interleaved A/B); at 256^3 too few tiles (73 against 66 us)
-            else if ((long long)((lc.L.nx + 62) / 64) * ((lc.L.ny + 6) / 8) * (lc.L.nz - 1) >= tune::ZR7_WIDE_MIN_TILES)
-                launch_zresrestrict_t<7, 64, 8, 512>(lf, lc, x, f, fc, xc, s, nch);
-            else launch_zresrestrict_t<7, 64, 4, 256>(lf, lc, x, f, fc, xc, s, nch);
-        } else {
-            // (fold levels: the SYM instances, whose residual is fold27's)
-            if (small && lf.fold) launch_zresrestrict_t<27, 16, 4, 64, true>(lf, lc, x, f, fc, xc, s, nch, tn);
-            else if (small) launch_zresrestrict_t<27, 16, 4, 64>(lf, lc, x, f, fc, xc, s, nch, tn);
-            else if (lf.fold)
-                launch_zresrestrict_t<27, tune::ZR27_CX, tune::ZR27_CY, 256, true>(lf, lc, x, f, fc, xc, s, nch, nullptr,
-                                                                                   nullptr, pn);
-            else launch_zresrestrict_t<27, 64, 4, 256>(lf, lc, x, f, fc, xc, s, nch, nullptr, nullptr, pn);
+        case ResidualKind::ZMARCH: {
+            const bool wide = p.nt == 512;  // 64 x 8 coarse points per workgroup (7-point levels)
+            if (skip_xc) xc = nullptr;
+            if (lr) {
+                if (wide) launch_zresrestrict_t<7, 64, 8, 512, false, true>(lf, lc, x, f, fc, xc, s, nch, nullptr, lr);
+                else launch_zresrestrict_t<7, 64, 4, 256, false, true>(lf, lc, x, f, fc, xc, s, nch, nullptr, lr);
+            } else if (fzero && p.fz) {
+                if (wide) launch_zresrestrict_t<7, 64, 8, 512, false, false, true>(lf, lc, x, f, fc, xc, s, nch);
+                else launch_zresrestrict_t<7, 64, 4, 256, false, false, true>(lf, lc, x, f, fc, xc, s, nch);
+            } else if (p.npoints == 7) {
+                if (p.small) launch_zresrestrict_t<7, 16, 4, 64>(lf, lc, x, f, fc, xc, s, nch, tn);
+                else if (wide) launch_zresrestrict_t<7, 64, 8, 512>(lf, lc, x, f, fc, xc, s, nch);
+                else launch_zresrestrict_t<7, 64, 4, 256>(lf, lc, x, f, fc, xc, s, nch);
+            } else {
+                if (p.small && p.sym) launch_zresrestrict_t<27, 16, 4, 64, true>(lf, lc, x, f, fc, xc, s, nch, tn);
+                else if (p.small) launch_zresrestrict_t<27, 16, 4, 64>(lf, lc, x, f, fc, xc, s, nch, tn);
+                else if (p.sym)
+                    launch_zresrestrict_t<27, tune::ZR27_CX, tune::ZR27_CY, 256, true>(lf, lc, x, f, fc, xc, s, nch, nullptr,
+                                                                                       nullptr, pn);
+                else launch_zresrestrict_t<27, 64, 4, 256>(lf, lc, x, f, fc, xc, s, nch, nullptr, nullptr, pn);
+            }
+            break;
         }
-        return;
+        case ResidualKind::GATHER: {  // (the kernel's last argument: it zeroes x_c)
+            const int np = p.npoints;
+            if (dim == 3 && np == 7)
+                hipLaunchKernelGGL((k_residual_restrict<3, 7>), gc, block, 0, s, lf.L, lc.L, x, f, fc, xc, lf.S, 1);
+            else if (dim == 3 && p.sym)
+                hipLaunchKernelGGL((k_residual_restrict<3, 27, true>), gc, block, 0, s, lf.L, lc.L, x, f, fc, xc, lf.S, 1);
+            else if (dim == 3)
+                hipLaunchKernelGGL((k_residual_restrict<3, 27>), gc, block, 0, s, lf.L, lc.L, x, f, fc, xc, lf.S, 1);
+            else if (np == 5)
+                hipLaunchKernelGGL((k_residual_restrict<2, 5>), gc, block, 0, s, lf.L, lc.L, x, f, fc, xc, lf.S, 1);
+            else
+                hipLaunchKernelGGL((k_residual_restrict<2, 9>), gc, block, 0, s, lf.L, lc.L, x, f, fc, xc, lf.S, 1);
+            break;
+        }
     }
-    dim3 block(64, 4, 1);
-    dim3 grid = grid3(lc.L.nx - 1, lc.L.ny - 1, lf.spec.dim == 3 ? lc.L.nz - 1 : 1, block);
-    const int dim = lf.spec.dim, np = lf.spec.npoints;
-    if (dim == 3 && np == 7)
-        hipLaunchKernelGGL((k_residual_restrict<3, 7>), grid, block, 0, s, lf.L, lc.L, x, f, fc, xc, lf.S, zero_xc);
-    else if (dim == 3 && lf.fold)
-        hipLaunchKernelGGL((k_residual_restrict<3, 27, true>), grid, block, 0, s, lf.L, lc.L, x, f, fc, xc, lf.S, zero_xc);
-    else if (dim == 3)
-        hipLaunchKernelGGL((k_residual_restrict<3, 27>), grid, block, 0, s, lf.L, lc.L, x, f, fc, xc, lf.S, zero_xc);
-    else if (np == 5)
-        hipLaunchKernelGGL((k_residual_restrict<2, 5>), grid, block, 0, s, lf.L, lc.L, x, f, fc, xc, lf.S, zero_xc);
-    else
-        hipLaunchKernelGGL((k_residual_restrict<2, 9>), grid, block, 0, s, lf.L, lc.L, x, f, fc, xc, lf.S, zero_xc);
 }
 
 // 2D Galerkin level: its last pre-sweep and the residual + restriction onto lc in one launch
@@ -1107,7 +1089,7 @@ void push_sweep(mgmc_handle* h, std::vector<int>& cur, int level, int direction,
     // fused prolongation on z-sweep levels (the 2D red-black kernel does not fold it: its staging
     // becomes a longer latency chain, 2D 1024^2 cycle 0.1292-0.1305 -> 0.1306-0.1316 ms against the
     // separate k_prolongate_pairs launch, measured in round 1)
-    const bool fold = lv.zsweep && !(h->paths & PATH_NO_FUSE_PROLONG);
+    const bool fold = lv.sweep == SweepKernel::ZSWEEP && !(h->paths & PATH_NO_FUSE_PROLONG);
     if (lv.pingpong() && pending_prolong && !fold) {
         h->ops.push_back({OP_PROLONGATE, level, 0, 0, 0});
         h->ops.back().src = cur[level];
@@ -1252,19 +1234,10 @@ void build_ops(mgmc_handle* h) {
 }
 
 // ---- the coarsest levels' sub-cycle in one workgroup (k_tail) ----
-constexpr size_t TAIL_LDS_LIMIT = 150 * 1024;
 // one 1024-thread workgroup (1024 / 512 / 256 threads: 256^3 cycle 0.529 / 0.538 / 0.570 ms, round 1)
 constexpr int TAIL_NT = 1024;
 
-// 3D plane stride padded to sp = 8 (mod 16) doubles: k_tail's colour passes give the two halves of a
-// half-wave the planes k and k+2, whose ds_read_b64 bank pairs (d mod 32) then sit 16 apart, so the
-// stride-2 class access is 2-way (the least a stride-2 access allows) instead of 4-way with sx odd
-// and unpadded planes (MI355X_MICROARCH.md LDS banking)
-long long tail_plane_stride(int nx, int ny) {
-    const long long sp = (long long)(nx + 1) * (ny + 1);
-    return sp + ((8 - sp % 16) + 16) % 16;
-}
-
+// k_tail's LDS layout of a level (plane stride: tail_plane_stride, mgmc_level_plan.hpp)
 Layout tail_layout(const Layout& L) {
     Layout G = L;
     G.off = 0;
@@ -1274,46 +1247,28 @@ Layout tail_layout(const Layout& L) {
     return G;
 }
 
-// the same choice from the level shapes alone (at creation time, before any level is allocated)
+// the tail start (mgmc_level_plan.hpp tail_start) from the level shapes alone: at creation time, before any
+// level is allocated
 int tail_start_by_size(const std::vector<LevelSpec>& specs, const mgmc_config& cfg, uint32_t paths, bool field) {
-    if ((paths & PATH_NO_TAIL) || field || cfg.coarse_solver != MGMC_COARSE_SSOR) return -1;
-    const int L = (int)specs.size();
-    for (int lt = 1; lt + 1 < L; ++lt) {
-        bool ok = true;
-        size_t tot = 0, vmax = 0;
-        for (int l = lt; l < L && ok; ++l) {
-            const LevelSpec& sp = specs[l];
-            ok = sp.npoints == (sp.dim == 3 ? 27 : 9);
-            const size_t v = sp.dim == 3 ? (size_t)tail_plane_stride(sp.n[0], sp.n[1]) * (sp.n[2] + 1)
-                                         : (size_t)(sp.n[0] + 1) * (sp.n[1] + 1);
-            tot += 2 * v;
-            vmax = std::max(vmax, v);
-        }
-        if (ok && (tot + vmax) * sizeof(double) <= TAIL_LDS_LIMIT) return lt;
-    }
-    return -1;
+    if (field || cfg.coarse_solver != MGMC_COARSE_SSOR) return -1;
+    return tail_start((int)specs.size(), paths, [&](int l, size_t* v, size_t*) {
+        const LevelSpec& sp = specs[l];
+        *v = tail_level_doubles(sp.dim, sp.n[0], sp.n[1], sp.n[2]);
+        return sp.npoints == (sp.dim == 3 ? 27 : 9);
+    });
 }
 
-// smallest level lt >= 1 whose levels lt .. L-1 all fit one workgroup's LDS (x, f per level + one
-// scratch of the largest + saved f on the rows of B): Galerkin levels, no low-rank part or a small
-// one (k_lr_small's), ordinary (in-place) sweeps, SSOR coarse sampler; -1 if none or only the
-// coarsest level fits (the coarse LDS kernel covers that)
+// ... and of the handle's levels (x, f per level + one scratch of the largest + saved f on the rows of B):
+// Galerkin levels, no low-rank part or a small one (k_lr_small's), ordinary (in-place) sweeps, SSOR
+// coarse sampler
 int tail_level(const mgmc_handle* h) {
-    if ((h->paths & PATH_NO_TAIL) || h->field_mode || h->cfg.coarse_solver != MGMC_COARSE_SSOR) return -1;
-    const int L = (int)h->levels.size();
-    for (int lt = 1; lt + 1 < L; ++lt) {
-        bool ok = true;
-        size_t tot = 0, vmax = 0;
-        for (int l = lt; l < L && ok; ++l) {
-            const Level& lv = h->levels[l];
-            ok = (lv.lr.m == 0 || lv.lr.small) && !lv.pingpong() && lv.spec.npoints == (lv.spec.dim == 3 ? 27 : 9);
-            const size_t v = (size_t)tail_layout(lv.L).nstore;
-            tot += 2 * v + (size_t)lv.lr.nrows;
-            vmax = std::max(vmax, v);
-        }
-        if (ok && (tot + vmax) * sizeof(double) <= TAIL_LDS_LIMIT) return lt;
-    }
-    return -1;
+    if (h->field_mode || h->cfg.coarse_solver != MGMC_COARSE_SSOR) return -1;
+    return tail_start((int)h->levels.size(), h->paths, [&](int l, size_t* v, size_t* extra) {
+        const Level& lv = h->levels[l];
+        *v = (size_t)tail_layout(lv.L).nstore;
+        *extra = (size_t)lv.lr.nrows;
+        return (lv.lr.m == 0 || lv.lr.small) && !lv.pingpong() && lv.spec.npoints == (lv.spec.dim == 3 ? 27 : 9);
+    });
 }
 
 void free_tails(mgmc_handle* h) {
@@ -1334,14 +1289,6 @@ void free_tails(mgmc_handle* h) {
     h->tail_jobs.clear();
     h->tail_njobs.clear();
     h->tail_zn.clear();
-}
-
-// the residual + restriction from level lf onto lf + 1 runs as the small z-marching kernel
-// (k_zresrestrict<., 16, 4, 64>): launch_residual_restrict's choice for zero_xc = 1
-bool zr_small_path(const mgmc_handle* h, int lf) {
-    const Level& f = h->levels[lf];
-    const Level& c = h->levels[lf + 1];
-    return f.spec.dim == 3 && !f.field && !(f.paths & PATH_NO_ZRESTRICT) && c.L.nx >= 8 && c.L.nx < 32;
 }
 
 // replace every maximal run of ops on levels >= lt (one call of build_ops_level(lt)) by one OP_TAIL
@@ -1451,11 +1398,11 @@ int build_tails_only(mgmc_handle* h) {
         }
 #endif
         // the sweeps' Box-Muller pairs: drawn by spare workgroups of the restriction before the tail when
-        // that is the small z-marching kernel (3D; k_zresrestrict<..., ZN>), else here
+        // that is the small z-marching kernel (ResidualPlan::tail_noise; k_zresrestrict<..., ZN>), else here
         std::vector<TailNoiseJob> jobs;
         long long zn = 0;
         const bool pre_zr = !out.empty() && out.back().kind == OP_RESIDUAL_RESTRICT && out.back().level == lt - 1 &&
-                            zr_small_path(h, lt - 1) && h->levels[lt - 1].lr.m == 0;
+                            h->levels[lt - 1].res.tail_noise && h->levels[lt - 1].lr.m == 0;
         for (int o = 0; o < A.nops; ++o) {
             TailOp& t = A.ops[o];
             t.zoff = -1;
@@ -1521,9 +1468,7 @@ bool qrestrict_ok(const mgmc_handle* h, int level) {
     if (h->paths & PATH_NO_QRESTRICT) return false;
     if (level < 1 || level + 1 >= (int)h->levels.size()) return false;
     const Level& lv = h->levels[level];
-    if (lv.spec.dim != 2 || lv.spec.npoints != 9 || !lv.quads || lv.jsweep || lv.field || lv.lr.m > 0 ||
-        !lv.pingpong())
-        return false;
+    if (lv.spec.dim != 2 || lv.spec.npoints != 9 || lv.sweep != SweepKernel::QUADS || lv.lr.m > 0) return false;
     if (qrestrict_threads(lv.L.nx / 2) == 0) return false;
     const int CJ = qrestrict_threads(lv.L.nx / 2) / (lv.L.nx / 2) - 3;
     return qrestrict_lds_bytes(lv.L.nx, CJ) <= 150 * 1024;
@@ -1607,12 +1552,11 @@ void mark_zero_inputs(mgmc_handle* h) {
             continue;
         const Level& lf = h->levels[rr.level];
         const Level& lc = h->levels[sw.level];
-        const bool zr = lf.spec.dim == 3 && !lf.field && !(lf.paths & PATH_NO_ZRESTRICT) && lc.L.nx >= 8;
         // j-marching levels and 3D quad-pass levels: out of place, x read only as the half-sweeps' input
-        const bool quads3 = lc.quads && lc.spec.dim == 3;
+        const bool halves = lc.sweep == SweepKernel::JSWEEP || (lc.sweep == SweepKernel::QUADS && lc.spec.dim == 3);
         // (low-rank levels too: the patches before a sweep change f only, the fix after it reads the
         // sweep's output, and the residual's dots read the fine level's x)
-        if (!zr || !(lc.jsweep || quads3) || lc.field) continue;
+        if (lf.res.kind != ResidualKind::ZMARCH || !halves) continue;
         rr.xzero = 1;
         sw.xzero = 1;
     }
@@ -1629,9 +1573,7 @@ void mark_zero_inputs(mgmc_handle* h) {
 // (the conditions themselves: mgmc_rhs_zero.hpp, host-only and tested on the CPU)
 static RhsZeroOp rhs_zero_op(const mgmc_handle* h, const Op& op) {
     const Level& lv = h->levels[op.level];
-    const bool has_coarse = op.level + 1 < (int)h->levels.size();
-    return RhsZeroOp{op.level, lv.zsweep, lv.lr.m, lv.spec.npoints, !(lv.paths & PATH_NO_ZRESTRICT),
-                     has_coarse ? h->levels[op.level + 1].L.nx : 0, tune::ZR_SMALL_NX, op.zpre};
+    return RhsZeroOp{op.level, lv.sweep == SweepKernel::ZSWEEP, lv.lr.m, lv.res.fz, op.zpre};
 }
 // returns whether any op's mark changed (the graphs embed the kernel choice: the caller rebuilds them)
 bool mark_rhs_zero(mgmc_handle* h) {
@@ -1663,7 +1605,7 @@ constexpr long long PN_MAX_PAIRS = 2LL << 20;
 
 //
 // The same for the first pre-sweep of a 3D quad-pass level after a 27-point z-marching residual +
-// restriction (zres_draws_noise): every workgroup of that launch draws its share of the coarse level's
+// restriction (ResidualPlan::pre_noise): every workgroup of that launch draws its share of the coarse level's
 // pairs after its own march (ZRestrictArgs::pn; the sweep then loads them, with xzero its known-zero
 // x too).  One buffer per level serves both: the pre-sweep reads it before the tail rewrites it.
 int plan_drawn_noise(mgmc_handle* h) {
@@ -1688,16 +1630,14 @@ int plan_drawn_noise(mgmc_handle* h) {
         }
         return buf[l];
     };
-    auto quad_consumer = [&](const Level& lv) {
-        return lv.spec.dim == 3 && !lv.field && lv.quads && !lv.jsweep && lv.pingpong();
-    };
+    auto quad_consumer = [&](const Level& lv) { return lv.spec.dim == 3 && lv.sweep == SweepKernel::QUADS; };
     for (size_t q = 0; q + 1 < h->ops.size(); ++q) {  // pre-sweeps: drawn by the restriction before them
         Op& rr = h->ops[q];
         Op& sw = h->ops[q + 1];
         if (rr.kind != OP_RESIDUAL_RESTRICT || rr.zpre != 0 || sw.kind != OP_SWEEP || sw.level != rr.level + 1) continue;
         const Level& lf = h->levels[rr.level];
         const Level& lc = h->levels[sw.level];
-        if (!zres_draws_noise(lf, lc) || !quad_consumer(lc) || (sw.xzero && sw.direction != MGMC_FORWARD)) continue;
+        if (!lf.res.pre_noise || !quad_consumer(lc) || (sw.xzero && sw.direction != MGMC_FORWARD)) continue;
         double2* b = level_buf(sw.level);
         if (!b) continue;
         rr.pn_dst = b;
@@ -1785,23 +1725,18 @@ void enqueue_ops(mgmc_handle* h, size_t begin, size_t end, hipStream_t s) {
                     lrr = LRRhsArg{lv.lr.rhs_e + nch};
                 else if (lr && lv.lr.dense_path)
                     fs = lv.lr.fe2;  // written with the level's residual
-                double* xo = lv.x;
-                if (lv.zsweep) {
-                    const Level* lc = op.prolong ? &h->levels[op.level + 1] : nullptr;
-                    xo = lv.buf(1 - op.src);
-                    launch_zsweep(lv, lv.buf(op.src), xo, fs, g, op.direction, lc, lc ? lc->x : nullptr,
-                                  h->cfg.coarse_scaling, s, nch, lrr.e ? &lrr : nullptr, op.fzero != 0);
-                } else if (lv.quads) {
-                    xo = lv.buf(1 - op.src);
-                    launch_quads(lv, lv.buf(op.src), xo, fs, g, op.direction, s, nch, op.xzero != 0, op.pnz);
-                } else if (lv.rb2d) {
-                    xo = lv.buf(1 - op.src);
-                    launch_rb2d(lv, lv.buf(op.src), xo, fs, g, op.direction, true, s, nch);
-                } else if (lv.pairs) {
-                    launch_pairs(lv, lv.x, fs, g, op.direction, s, nch);
-                } else {
-                    launch_sweep(lv, lv.x, fs, g, op.direction, true, s, nch);
+                SweepOpts so;
+                if (op.prolong) {  // (z-sweep levels: push_sweep)
+                    so.coarse = &h->levels[op.level + 1];
+                    so.xc = so.coarse->x;
                 }
+                so.alpha = h->cfg.coarse_scaling;
+                so.lrr = lrr.e ? &lrr : nullptr;
+                so.fzero = op.fzero != 0;
+                so.xzero = op.xzero != 0;
+                so.zb = op.pnz;
+                // (in-place levels: op.src is 0, the canonical buffer)
+                double* xo = launch_level_sweep(lv, lv.buf(op.src), lv.buf(1 - op.src), fs, g, op.direction, s, nch, so);
                 if (lr && lv.lr.small)
                     lr_small(h, lv, xo, op.direction, op.lr_next, op.lr_next_tag, sample, s, nch);
                 else if (lr)
@@ -1846,7 +1781,7 @@ void enqueue_ops(mgmc_handle* h, size_t begin, size_t end, hipStream_t s) {
                     const int ti = op.zpre - 1;
                     const TailNoiseLaunch tn{h->tail_jobs[ti], h->tail_njobs[ti], h->tail_zb[ti], h->tail_zn[ti],
                                              h->key, (uint32_t)h->chain, (uint32_t)(h->seed >> 32), sample};
-                    launch_residual_restrict(lv, lc, lv.buf(op.src), fr, lc.f, lc.x, 1, s, nch, &tn);
+                    launch_residual_restrict(lv, lc, lv.buf(op.src), fr, lc.f, lc.x, s, nch, &tn);
                 } else {
                     PreNoiseLaunch pnl;
                     if (op.pn_dst) {
@@ -1854,7 +1789,7 @@ void enqueue_ops(mgmc_handle* h, size_t begin, size_t end, hipStream_t s) {
                         pnl.key = h->key;
                         pnl.sample = sample;
                     }
-                    launch_residual_restrict(lv, lc, lv.buf(op.src), fr, lc.f, lc.x, 1, s, nch, nullptr, op.xzero != 0,
+                    launch_residual_restrict(lv, lc, lv.buf(op.src), fr, lc.f, lc.x, s, nch, nullptr, op.xzero != 0,
                                              lrr.e ? &lrr : nullptr, op.pn_dst ? &pnl : nullptr, op.fzero != 0);
                     if (op.xzero && h->poison)  // (debug) the skipped x_c write leaves stale values: make them NaN
                         for (int c = 0; c < nch; ++c)
@@ -2195,13 +2130,6 @@ int mgmc_describe(const mgmc_config* cfg, mgmc_level_desc* out, int max_levels) 
 }
 
 // the kernel families that address level l (the launch_* dispatch of this handle) and their check
-static int zrestrict_cx_of(const mgmc_handle* h, int l) {  // launch_residual_restrict's tile width
-    if (l + 1 >= (int)h->levels.size()) return 0;
-    const Level& lf = h->levels[l];
-    const Level& lc = h->levels[l + 1];
-    if (lf.spec.dim != 3 || lf.field || (lf.paths & PATH_NO_ZRESTRICT) || lc.L.nx < 8) return 0;
-    return lc.L.nx < 32 ? 16 : (lf.spec.npoints == 27 && lf.fold ? tune::ZR27_CX : 64);
-}
 // both directions and both halves of a j-marching level, with launch_jsweep's plan (short_grid: the plan
 // with its last 8 workgroups dropped -- a negative control for the test, which the replay must reject)
 static std::string jsweep_grid_check_level(const Layout& L, int num_cu, bool short_grid = false) {
@@ -2218,17 +2146,17 @@ static std::string jsweep_grid_check_level(const Layout& L, int num_cu, bool sho
 static std::string check_level_layout_of(const mgmc_handle* h, int l) {
     const Level& lv = h->levels[l];
     unsigned fam = LF_POINT;
-    if (lv.pairs || lv.quads) fam |= LF_PAIRS;
-    if (lv.zsweep) fam |= LF_ZSWEEP;
-    if (lv.rb2d) fam |= LF_RB2D;
-    const int cx = zrestrict_cx_of(h, l);
+    if (sweep_pair_items(lv.sweep)) fam |= LF_PAIRS;
+    if (lv.sweep == SweepKernel::ZSWEEP) fam |= LF_ZSWEEP;
+    if (lv.sweep == SweepKernel::RB2D) fam |= LF_RB2D;
+    const int cx = lv.res.cx;  // (z-marching residual + restriction only)
     if (cx) fam |= LF_ZRESTRICT;
-    if (l > 0 && h->levels[l - 1].zsweep) fam |= LF_ZSWEEP_C;
-    if (lv.jsweep) fam |= LF_JSWEEP;
+    if (l > 0 && h->levels[l - 1].sweep == SweepKernel::ZSWEEP) fam |= LF_ZSWEEP_C;
+    if (lv.sweep == SweepKernel::JSWEEP) fam |= LF_JSWEEP;
     if (qrestrict_ok(h, l)) fam |= LF_QRESTRICT;
     const int reach = lv.field && (lv.F.scheme == 9 || lv.F.scheme == 27) ? 2 : 1;
     std::string e = check_level_layout(lv.L, fam, reach, cx);
-    if (e.empty() && lv.jsweep) e = jsweep_grid_check_level(lv.L, lv.num_cu);
+    if (e.empty() && lv.sweep == SweepKernel::JSWEEP) e = jsweep_grid_check_level(lv.L, lv.num_cu);
     return e;
 }
 
@@ -2349,16 +2277,13 @@ static int create_impl(const mgmc_config* cfg, const CsrHost* csr, int device, u
             hipMemcpyAsync(coef, fh.coef.data(), fh.coef.size() * sizeof(double), hipMemcpyHostToDevice, h->stream);
             hipMemsetAsync(lv.rbuf, 0, bytes, h->stream);
         }
-        // fused z-marching sweep: fine 3D 7-point levels whose row splits into 64-pair tiles
-        const double* st = lv.spec.st;  // the z-sweep folds the symmetric FD stencil to 4 coefficients
-        const bool symmetric = st[4] == st[22] && st[10] == st[16] && st[12] == st[14];
-        lv.zsweep = !lv.field && cfg->dim == 3 && lv.spec.npoints == 7 && symmetric && l + 1 < specs.size() &&
-                    (lv.L.nx % (2 * ZS_XP)) == 0 && !(h->paths & PATH_NO_ZSWEEP);
-        lv.pairs = !lv.field && pairs_eligible(lv.spec, lv.L) && !(h->paths & PATH_NO_PAIRS);
-        lv.rb2d = !lv.field && cfg->dim == 2 && lv.spec.npoints == 5 && l + 1 < specs.size() &&
-                  !(h->paths & PATH_NO_RB2D);
-        lv.jsweep = lv.pairs && jsweep_eligible(lv.spec, lv.L, h->paths) && (tail0 < 0 || (int)l < tail0);
-        lv.quads = lv.jsweep || (lv.pairs && quads_eligible(lv.spec, lv.L, h->paths) && (tail0 < 0 || (int)l < tail0));
+        // the level's kernels, decided here once (mgmc_level_plan.hpp)
+        const double* st = lv.spec.st;
+        const bool has_coarser = l + 1 < specs.size();
+        const LevelShape sh{cfg->dim, lv.spec.npoints, lv.L.nx, lv.L.ny, lv.L.nz, lv.field,
+                            st[4] == st[22] && st[10] == st[16] && st[12] == st[14], lv.fold, has_coarser};
+        lv.sweep = plan_sweep(sh, h->paths, (int)l, tail0);
+        if (has_coarser) lv.res = plan_residual(sh, h->paths, specs[l + 1].n[0], specs[l + 1].n[1], specs[l + 1].n[2]);
         if (lv.pingpong()) {
             if (hipMalloc(&lv.x2, cbytes) != hipSuccess) {
                 h->levels.push_back(lv);
@@ -2645,34 +2570,32 @@ int mgmc_level_kernels(const mgmc_handle* h, int level, char* out, size_t n) {
         sweep = "k_tail<" + std::to_string(dim) + ">";
     } else if (last) {
         sweep = h->cfg.coarse_solver == MGMC_COARSE_CHOLESKY ? (h->chol_B > 0 ? "k_coarse_chol_blocked" : "k_coarse_chol") : "k_coarse_ssor_lds (or separate colour passes)";
-    } else if (lv.field) {
-        sweep = "k_fsweep<" + std::to_string(dim) + ">";
-    } else if (lv.zsweep) {
-        sweep = "k_zsweep_rb7<32," + std::to_string(zsweep_plain_rows(lv, h->nchains)) + ",...,0>";
-        if (!(h->paths & PATH_NO_FUSE_PROLONG)) post = "k_zsweep_rb7<32," + std::to_string(tune::ZS_TYP) + ",...,PROLONG>";
-    } else if (lv.jsweep) {
-        sweep = "k_jsweep_half<" + std::to_string(lv.L.nx / 2) + (lv.sym && lv.L.nx == 256 ? ",sym" : "") + ">";
-    } else if (lv.quads) {
-        sweep = "k_sweep_quads<" + std::to_string(dim) + ">";
-    } else if (lv.rb2d) {
-        sweep = "k_rb2d";
-    } else if (lv.pairs) {
-        sweep = "k_sweep_pairs<" + std::to_string(dim) + ">";
     } else {
-        sweep = (np == 2 * dim + 1 ? "k_sweep_rb<" : "k_sweep_mc<") + std::to_string(dim) + ">";
+        const std::string d = std::to_string(dim);
+        switch (lv.sweep) {
+            case SweepKernel::FIELD: sweep = "k_fsweep<" + d + ">"; break;
+            case SweepKernel::ZSWEEP:
+                sweep = "k_zsweep_rb7<32," + std::to_string(zsweep_plain_rows(lv, h->nchains)) + ",...,0>";
+                if (!(h->paths & PATH_NO_FUSE_PROLONG))
+                    post = "k_zsweep_rb7<32," + std::to_string(tune::ZS_TYP) + ",...,PROLONG>";
+                break;
+            case SweepKernel::JSWEEP:
+                sweep = "k_jsweep_half<" + std::to_string(lv.L.nx / 2) + (lv.sym && lv.L.nx == 256 ? ",sym" : "") + ">";
+                break;
+            case SweepKernel::QUADS: sweep = "k_sweep_quads<" + d + ">"; break;
+            case SweepKernel::RB2D: sweep = "k_rb2d"; break;
+            case SweepKernel::PAIRS: sweep = "k_sweep_pairs<" + d + ">"; break;
+            case SweepKernel::COLOUR: sweep = (np == 2 * dim + 1 ? "k_sweep_rb<" : "k_sweep_mc<") + d + ">"; break;
+        }
     }
     if (!last && !(tl >= 0 && level >= tl)) {
-        const int cx = zrestrict_cx_of(h, level);
-        if (lv.field) res = "k_fresidual + k_restrict";
-        else if (cx) {
-            const Level& lc = h->levels[level + 1];
-            const bool wide = np == 7 && cx == 64 &&
-                              (long long)((lc.L.nx + 62) / 64) * ((lc.L.ny + 6) / 8) * (lc.L.nz - 1) >= tune::ZR7_WIDE_MIN_TILES;
-            res = "k_zresrestrict<" + std::to_string(np) + "," + std::to_string(cx) + "," + (wide ? "8" : "4") + ">";
+        const ResidualPlan& p = lv.res;
+        if (p.kind == ResidualKind::FIELD) res = "k_fresidual + k_restrict";
+        else if (p.kind == ResidualKind::ZMARCH) {
+            res = "k_zresrestrict<" + std::to_string(np) + "," + std::to_string(p.cx) + "," + std::to_string(p.cy) + ">";
         } else if (qrestrict_ok(h, level)) {
             sweep = "k_sweep_quads<2> (last pre-sweep: k_quads_restrict2d)";
             res = "k_quads_restrict2d";
-
         } else res = "k_residual_restrict<" + std::to_string(dim) + "," + std::to_string(np) + ">";
     }
     std::string text = "sweep=" + sweep;
@@ -2700,7 +2623,7 @@ int mgmc_level_kernels(const mgmc_handle* h, int level, char* out, size_t n) {
     if (lv.lr.m > 0)
         text += std::string(";lowrank=") + (lv.lr.rhs_inplace ? "dense,rhs_inplace" : lv.lr.dense_path ? "dense"
                                              : lv.lr.small ? "small" : "rows");
-    // a 3D quad-pass level whose row length takes the three-load window instances (quads_lanes)
+    // a 3D quad-pass level whose row length takes the three-load window instances (quads_lanes, mgmc_level_plan.hpp)
     if (sweep == "k_sweep_quads<3>" && !quads_lanes(dim, lv.L.nx / 2)) text += ";quads=window";
     snprintf(out, n, "%s", text.c_str());
     return MGMC_OK;
@@ -2988,19 +2911,11 @@ static int sweep_component(mgmc_handle* h, int level, int direction, int nsweeps
         double* fb = lv.scratch[0];
         if (lr && noise) fb = lr_rhs(h, lv, LR_PATCH_NOISE, lv.scratch[0], tag + (uint32_t)s, h->ctrl + 3, h->stream);
         lds_poison(h, lv, h->stream);  // (debug: as enqueue_ops) the sweep starts on NaN-filled LDS
-        if (noise && lv.zsweep) {  // the fused z-marching kernel of the V-cycle (out of place)
-            launch_zsweep(lv, lv.scratch[cur], lv.scratch[3 - cur], fb, g, direction, nullptr, nullptr, 0.0, h->stream);
-            cur = 3 - cur;
-        } else if (noise && lv.quads) {  // two colour pairs per launch (out of place)
-            launch_quads(lv, lv.scratch[cur], lv.scratch[3 - cur], fb, g, direction, h->stream);
-            cur = 3 - cur;
-        } else if (noise && lv.rb2d) {  // one-launch 2D red-black sweep (out of place)
-            launch_rb2d(lv, lv.scratch[cur], lv.scratch[3 - cur], fb, g, direction, true, h->stream);
-            cur = 3 - cur;
-        } else if (noise && lv.pairs) {  // the colour-pair passes of the V-cycle (in place)
-            launch_pairs(lv, lv.scratch[cur], fb, g, direction, h->stream);
+        if (noise) {  // the V-cycle's kernel for this level; the out-of-place ones write the other scratch buffer
+            if (launch_level_sweep(lv, lv.scratch[cur], lv.scratch[3 - cur], fb, g, direction, h->stream) != lv.scratch[cur])
+                cur = 3 - cur;
         } else {
-            launch_sweep(lv, lv.scratch[cur], fb, g, direction, noise, h->stream);
+            launch_sweep(lv, lv.scratch[cur], fb, g, direction, false, h->stream);
         }
         if (lr) {
             lds_poison(h, lv, h->stream);
@@ -3125,7 +3040,7 @@ int mgmc_residual_restrict(mgmc_handle* h, int level, const double* f, const dou
         fr = lr_rhs(h, lf, LR_PATCH_RESIDUAL, lf.scratch[0], 0, h->ctrl + 3, h->stream);
     }
     if (lf.lr.m > 0) lds_poison(h, lf, h->stream);  // (the low-rank launches above wrote LDS again)
-    launch_residual_restrict(lf, lc, lf.scratch[1], fr, lc.scratch[0], lc.scratch[1], 1, h->stream);
+    launch_residual_restrict(lf, lc, lf.scratch[1], fr, lc.scratch[0], lc.scratch[1], h->stream);
     HIPCHK(h, hipGetLastError());
     return download(h, level + 1, lc.scratch[0], fc);
 }
@@ -3164,10 +3079,10 @@ int mgmc_time_fine_sweeps(mgmc_handle* h, int nsweeps, float* ms) {
         GibbsArg g = make_gibbs(h, lv, 0x80000000u + (uint32_t)s, 0, h->ctrl);
         const int dir = (s & 1) ? MGMC_BACKWARD : MGMC_FORWARD;
         lds_poison(h, lv, h->stream);  // (debug only: the time then includes the fill)
-        if (lv.zsweep) {
+        if (lv.sweep == SweepKernel::ZSWEEP) {
             launch_zsweep(lv, lv.scratch[cur], lv.scratch[3 - cur], lv.f, g, dir, nullptr, nullptr, 0.0, h->stream);
             cur = 3 - cur;
-        } else if (lv.rb2d) {
+        } else if (lv.sweep == SweepKernel::RB2D) {
             launch_rb2d(lv, lv.scratch[cur], lv.scratch[3 - cur], lv.f, g, dir, true, h->stream);
             cur = 3 - cur;
         } else {

@@ -2,6 +2,7 @@
 // (mgmc_handle: levels, op list, graphs, low-rank / Cholesky / solver / RCCL state), its per-level
 // Level and LowRankDev, the kernel-path switches (MGMC_DISABLE), error helpers, and the launch /
 // orchestration helpers one unit defines and another calls.
+//   mgmc_level_plan.hpp    which kernels a level runs (host-only: Level::sweep, Level::res, MGMC_DISABLE)
 //   mgmc_capi.hip          launchers, the cycle's op list and graphs, create / destroy, the Sampler
 //                          and component entry points
 //   mgmc_chol_setup.hip    the coarsest level's Cholesky factors (build_coarse_chol)
@@ -44,6 +45,7 @@ static_assert(MGMC_LAYOUT_POINT == mgmc::LF_POINT && MGMC_LAYOUT_PAIRS == mgmc::
 #include "mgmc_cholesky.hpp"
 #include "mgmc_field.hpp"
 #include "mgmc_operators.hpp"
+#include "mgmc_level_plan.hpp"
 #include "mgmc_rhs_zero.hpp"
 #include "mgmc_fieldstats.hpp"
 
@@ -98,78 +100,10 @@ struct Op {
 };
 
 
-// Kernel-path switches.  Every default fast path has a general fallback (the same arithmetic, bitwise
-// equal); MGMC_DISABLE=<comma list> turns fast paths off at mgmc_create so the variant tests
-// (tests/test_gpu_parity.py test_variant_cycles_bitwise, test_gpu_lowrank.py) can run the fallbacks
-// on shapes where the fast path would be taken.  Read once per handle; unknown tokens are an error.
-enum PathFlag : uint32_t {
-    PATH_NO_TAIL = 1u << 0,               // coarsest levels as separate launches instead of k_tail
-    PATH_NO_FUSE_PROLONG = 1u << 1,       // separate prolongate-add pass before the first post-sweep
-    PATH_NO_QUADS = 1u << 2,              // colour-pair passes instead of two pairs per launch
-    PATH_NO_RB2D = 1u << 3,               // 2D fine level: colour passes instead of k_rb2d
-    PATH_NO_ZSWEEP = 1u << 4,             // 3D fine level: colour passes instead of k_zsweep_rb7
-    PATH_NO_PAIRS = 1u << 5,              // Galerkin levels: per-colour passes instead of pair passes
-    PATH_NO_ZRESTRICT = 1u << 6,          // residual + restriction: per-point gather kernel
-    PATH_NO_LR_SMALL = 1u << 7,           // low-rank fix: generic multi-launch path instead of k_lr_small
-    PATH_NO_LR_MERGE = 1u << 8,           // low-rank: separate restore / patch launches around restriction
-    PATH_NO_LR_DENSE = 1u << 9,           // dense low-rank column: the row lists over every vertex
-    PATH_NO_CHOL_DENSE = 1u << 10,        // coarse Cholesky: the blocked banded solves at any size
-    PATH_NO_JSWEEP = 1u << 11,            // 3D Galerkin levels of 64 / 128 pairs: colour-pair passes, not j-marching halves
-    PATH_NO_QRESTRICT = 1u << 12,         // 2D Galerkin levels: last pre-sweep and residual + restriction as two launches
-    PATH_NO_PROLONG_Z = 1u << 13,         // big 3D levels: the per-point prolongation instead of the z-marching one
-    PATH_NO_XZERO = 1u << 14,             // the restriction zeroes x_{l+1} and its first pre-sweep loads it
-    PATH_NO_FOLD = 1u << 15,              // 3D fold levels: residuals in the reference's CSR order, not fold27's
-    PATH_NO_POST_NOISE = 1u << 16,        // every sweep draws its own noise (none drawn by a restriction / tail launch)
-};
-
-struct PathToken {
-    const char* name;
-    uint32_t flag;
-};
-constexpr PathToken kPathTokens[] = {
-    {"tail", PATH_NO_TAIL},           {"fuse_prolong", PATH_NO_FUSE_PROLONG},
-    {"quads", PATH_NO_QUADS},         {"rb2d", PATH_NO_RB2D},
-    {"zsweep", PATH_NO_ZSWEEP},       {"pairs", PATH_NO_PAIRS},
-    {"zrestrict", PATH_NO_ZRESTRICT}, {"lr_small", PATH_NO_LR_SMALL},
-    {"lr_merge", PATH_NO_LR_MERGE},   {"lr_dense", PATH_NO_LR_DENSE},
-    {"chol_dense", PATH_NO_CHOL_DENSE}, {"jsweep", PATH_NO_JSWEEP},
-    {"qrestrict", PATH_NO_QRESTRICT}, {"prolong_z", PATH_NO_PROLONG_Z},
-    {"xzero", PATH_NO_XZERO},         {"fold", PATH_NO_FOLD},
-    {"post_noise", PATH_NO_POST_NOISE},
-};
-
-// parse MGMC_DISABLE; returns false (and the offending token in *bad) for an unknown token
-inline bool read_path_flags(uint32_t* flags, std::string* bad) {
-    *flags = 0;
-    const char* e = getenv("MGMC_DISABLE");
-    if (!e) return true;
-    std::string list(e);
-    size_t pos = 0;
-    while (pos <= list.size()) {
-        size_t end = list.find(',', pos);
-        if (end == std::string::npos) end = list.size();
-        const std::string tok = list.substr(pos, end - pos);
-        if (!tok.empty()) {
-            bool found = false;
-            for (const PathToken& t : kPathTokens)
-                if (tok == t.name) {
-                    *flags |= t.flag;
-                    found = true;
-                }
-            if (!found) {
-                *bad = tok;
-                return false;
-            }
-        }
-        pos = end + 1;
-    }
-    return true;
-}
-
 // z-marching sweep tile shape (mgmc_zsweep.hpp): 32 x-pairs x TY rows, TY/2 core waves + 2 halo
 // waves rounded up to a multiple of four (768 threads for TY 16); two workgroups per CU need <= 80
 // VGPRs (6 waves per SIMD).  Values in mgmc_tuning.hpp, tuning history in DESIGN.md.
-constexpr int ZS_XP = 32, ZS_TY = tune::ZS_TY, ZS_NT = zs_threads(ZS_TY), ZS_MINW = tune::ZS_MINW,
+constexpr int ZS_TY = tune::ZS_TY, ZS_NT = zs_threads(ZS_TY), ZS_MINW = tune::ZS_MINW,
               ZS_TZ = tune::ZS_TZ, ZS_TYP = tune::ZS_TYP, ZS_NTP = zs_threads(ZS_TYP),
               ZS_MINWP = tune::ZS_MINWP, ZS_TZP = tune::ZS_TZP;
 
@@ -244,17 +178,14 @@ struct Level {
     size_t lds_bytes = 0;  // >0 if the whole-level LDS kernel can hold x and f
     int num_cu = 256;      // compute units of the handle's device (grid sizing; MI355X: 256)
     uint32_t paths = 0;    // PathFlag bits of the handle (MGMC_DISABLE)
-    bool zsweep = false;   // fused z-marching red-black sweep available
-    bool pairs = false;    // Galerkin level swept in colour-pair passes (mgmc_gsweep.hpp)
-    bool quads = false;    // ... two pairs per launch, out of place (k_sweep_quads, or k_jsweep_half:)
-    bool jsweep = false;   // ... j-marching half-sweeps (mgmc_jsweep.hpp)
-    bool rb2d = false;     // 2D 5-point level: one-launch red-black sweep, out of place (k_rb2d)
+    SweepKernel sweep = SweepKernel::COLOUR;  // the level's noisy sweep (mgmc_level_plan.hpp plan_sweep)
+    ResidualPlan res;      // its residual + restriction onto the next level (plan_residual)
     bool field = false;    // per-vertex coefficients (mgmc_create_csr, mgmc_field.hpp)
     bool sym = false;      // 27-point stencil bitwise reflection-symmetric: kernels fold it (stencil_coef<true>)
     bool fold = false;     // ... and its residuals take the class-folded sum (fold27; MGMC_DISABLE=fold: CSR order)
     FieldArg F;            // ... their device field, pattern and colouring
     double* rbuf = nullptr;  // ... residual scratch (padded layout, zero boundary)
-    bool pingpong() const { return zsweep || quads || rb2d; }  // out-of-place sweeps: x <-> x2
+    bool pingpong() const { return sweep_pingpong(sweep); }  // out-of-place sweeps: x <-> x2
     double* buf(int i) const { return i == 0 ? x : x2; }
     LowRankDev lr;
 };
@@ -413,12 +344,10 @@ dim3 grid3(int nthreads_x, int nrows_y, int nz_blocks, dim3 block);
 GibbsArg make_gibbs(const mgmc_handle* h, const Level& lv, uint32_t tag, int colour, const uint64_t* sample);
 void launch_sweep(const Level& lv, double* x, const double* f, const GibbsArg& g0, int direction, bool noise,
                   hipStream_t s, int nch = 1);
-bool zres_lrf_capable(const Level& lf, const Level& lc);
 void launch_residual_restrict(const Level& lf, const Level& lc, const double* x, const double* f, double* fc,
-                              double* xc, int zero_xc, hipStream_t s, int nch = 1, const TailNoiseLaunch* tn = nullptr,
+                              double* xc, hipStream_t s, int nch = 1, const TailNoiseLaunch* tn = nullptr,
                               bool skip_xc = false, const LRRhsArg* lr = nullptr, const PreNoiseLaunch* pn = nullptr,
                               bool fzero = false);
-bool zres_draws_noise(const Level& lf, const Level& lc);
 void launch_prolongate(const Level& lf, const Level& lc, double* x, const double* xc, double alpha, hipStream_t s,
                        int nch = 1);
 void lr_dots(const Level& lv, const double* v, LRScale scale, hipStream_t s, int nch = 1);

@@ -190,8 +190,7 @@ int lr_setup_level(mgmc_handle* h, int level, const std::vector<LRColumn>& cols,
         }
         // the fine z-sweep level's kernels read the patched right-hand side in place (k_zsweep_rb7 /
         // k_zresrestrict LRF) when B_g is one number
-        r.rhs_inplace = r.dense_path && r.split_g >= 0 && lv.zsweep && level + 1 < (int)h->levels.size() &&
-                        zres_lrf_capable(lv, h->levels[level + 1]);
+        r.rhs_inplace = r.dense_path && r.split_g >= 0 && lv.sweep == SweepKernel::ZSWEEP && lv.res.lrf;
         if (r.rhs_inplace) {
             std::vector<double> ez((size_t)2 * h->nchains, 0.0);
             if ((rc = lr_to_device(h, r, &r.rhs_e, ez))) return rc;

@@ -30,13 +30,11 @@ inline uint64_t rhs_or_bits(const double* v, size_t n) {
 // what the choice depends on, for one op of the cycle
 struct RhsZeroOp {
     int level;         // the op's level
-    bool zsweep;       // the level runs k_zsweep_rb7 (Level::zsweep)
+    bool zsweep;       // the level runs k_zsweep_rb7 (Level::sweep)
     int lr_m;          // low-rank columns of the level (a posterior level patches f: never zero)
-    int npoints;       // stencil size of the level
-    bool zrestrict;    // the z-marching residual + restriction is not switched off (MGMC_DISABLE=zrestrict)
-    int coarse_nx;     // cells per row of the next coarser level
-    int small_nx;      // below it the residual runs the small 16 x 4 kernel (tune::ZR_SMALL_NX), which has no FZ
-                       // instance: a z-sweep level has nx >= 64, so its coarse level has nx >= 32 and never is small
+    bool residual_fz;  // the level's residual + restriction has an FZ instance (ResidualPlan::fz, mgmc_level_plan.hpp:
+                       // the 7-point z-marching kernel, not the small 16 x 4 one -- a z-sweep level has nx >= 64, so
+                       // its coarse level has nx >= 32 and never is small -- and not the gather kernel)
     int zpre;          // Op::zpre of a residual + restriction (its spare workgroups draw a tail's noise: small kernel)
 };
 
@@ -45,8 +43,7 @@ inline bool rhs_zero_sweep_ok(bool f0_zero, const RhsZeroOp& o) {
 }
 
 inline bool rhs_zero_residual_ok(bool f0_zero, const RhsZeroOp& o) {
-    return f0_zero && o.level == 0 && o.zsweep && o.lr_m == 0 && o.npoints == 7 && o.zrestrict && o.zpre == 0 &&
-           o.coarse_nx >= 8 && o.coarse_nx >= o.small_nx;
+    return f0_zero && o.level == 0 && o.zsweep && o.lr_m == 0 && o.residual_fz && o.zpre == 0;
 }
 
 }  // namespace mgmc_host

@@ -40,7 +40,7 @@ void mg_precond(mgmc_handle* h, int level, double* x, double* f, hipStream_t s) 
             lr_dots(lv, x, LR_SCALE_INV, s);
             fr = lr_rhs(h, lv, LR_PATCH_RESIDUAL, f, 0, h->ctrl + 3, s);
         }
-        launch_residual_restrict(lv, lc, x, fr, lc.scratch[1], lc.scratch[0], 1, s);  // zeroes x_{l+1}
+        launch_residual_restrict(lv, lc, x, fr, lc.scratch[1], lc.scratch[0], s);  // zeroes x_{l+1}
         if (lv.lr.m > 0) lr_restore(lv, f, s);
         mg_precond(h, level + 1, lc.scratch[0], lc.scratch[1], s);
         launch_prolongate(lv, lc, x, lc.scratch[0], c.coarse_scaling, s);

@@ -1,0 +1,191 @@
+// The host-side level plan (multigridmc_amd/csrc/mgmc_level_plan.hpp), compiled alone by
+// tests/test_level_plan_host.py (g++, AddressSanitizer + UBSan): which sweep and which residual + restriction
+// kernel each level of a hierarchy gets, and where k_tail starts.  The expected plans are the labels the merged
+// GPU tests assert for the same shapes (named at each block), not values taken from the header.  Prints one
+// "ok <name>" line per check; exits 1 on a failure.
+#include <cstdio>
+#include <cstdlib>
+#include <string>
+#include <vector>
+
+#include "mgmc_level_plan.hpp"
+
+using namespace mgmc_host;
+using SK = SweepKernel;
+using RK = ResidualKind;
+
+static int failures = 0;
+static void check(bool ok, const std::string& name) {
+    std::printf("%s %s\n", ok ? "ok" : "FAIL", name.c_str());
+    if (!ok) ++failures;
+}
+
+struct Hier {
+    std::vector<LevelShape> sh;
+    std::vector<SK> sweep;
+    std::vector<ResidualPlan> res;
+    int tail = -1;
+};
+
+// The hierarchy of an n[0] x n[1] x n[2] lattice by halving, as mgmc_create builds it: the FD prior's fine level
+// has the symmetric 5 / 7-point stencil and Galerkin levels of 9 / 27 points whose 3D stencils are
+// reflection-symmetric (fold); the FEM prior has 9 / 27 points on every level, not symmetric bit for bit.
+static Hier walk(int dim, int nx, int ny, int nz, int nlevel, bool fem, uint32_t paths) {
+    Hier H;
+    for (int l = 0; l < nlevel; ++l) {
+        const bool galerkin = fem || l > 0;
+        LevelShape s;
+        s.dim = dim;
+        s.npoints = dim == 3 ? (galerkin ? 27 : 7) : (galerkin ? 9 : 5);
+        s.nx = nx >> l;
+        s.ny = ny >> l;
+        s.nz = dim == 3 ? nz >> l : 0;
+        s.field = false;
+        s.fd_symmetric = !fem;
+        s.fold = dim == 3 && !fem && l > 0 && !(paths & PATH_NO_FOLD);
+        s.has_coarser = l + 1 < nlevel;
+        H.sh.push_back(s);
+    }
+    H.tail = tail_start(nlevel, paths, [&](int l, size_t* v, size_t*) {
+        const LevelShape& s = H.sh[l];
+        *v = tail_level_doubles(s.dim, s.nx, s.ny, s.nz);
+        return s.npoints == (s.dim == 3 ? 27 : 9);
+    });
+    for (int l = 0; l < nlevel; ++l) {
+        H.sweep.push_back(plan_sweep(H.sh[l], paths, l, H.tail));
+        H.res.push_back(l + 1 < nlevel ? plan_residual(H.sh[l], paths, H.sh[l + 1].nx, H.sh[l + 1].ny, H.sh[l + 1].nz)
+                                       : ResidualPlan());
+    }
+    return H;
+}
+
+// the levels from lt on keep in-place sweeps, so k_tail can run them
+static bool in_place_from(const Hier& H, int lt) {
+    bool ok = true;
+    for (size_t l = (size_t)lt; l < H.sweep.size(); ++l) ok = ok && !sweep_pingpong(H.sweep[l]);
+    return ok;
+}
+
+static bool zmarch(const ResidualPlan& p, int np, int cx, int cy) {
+    return p.kind == RK::ZMARCH && p.npoints == np && p.cx == cx && p.cy == cy;
+}
+
+// a 7-point level's plan onto a coarse level of cnx x cny x cnz cells
+static ResidualPlan fine_res(int cnx, int cny, int cnz, uint32_t paths = 0) {
+    const LevelShape s{3, 7, 2 * cnx, 2 * cny, 2 * cnz, false, true, false, true};
+    return plan_residual(s, paths, cnx, cny, cnz);
+}
+
+static uint32_t flag_of(const char* token) {
+    setenv("MGMC_DISABLE", token, 1);
+    uint32_t f = 0;
+    std::string bad;
+    const bool ok = read_path_flags(&f, &bad);
+    unsetenv("MGMC_DISABLE");
+    return ok ? f : 0;
+}
+
+int main() {
+    {  // 512^3, 7 levels: tests/test_gpu_headline.py test_headline_kernel_instances
+        const Hier H = walk(3, 512, 512, 512, 7, false, 0);
+        check(H.sweep[0] == SK::ZSWEEP, "headline_l0_zsweep");
+        const ResidualPlan& r0 = H.res[0];
+        check(zmarch(r0, 7, 64, 8) && r0.nt == 512 && !r0.small && !r0.sym, "headline_l0_residual_7_64_8");
+        check(r0.fz && r0.lrf && !r0.pre_noise && !r0.tail_noise, "headline_l0_residual_fz_lrf");
+        check(H.sweep[1] == SK::JSWEEP && H.sh[1].nx / 2 == 128, "headline_l1_jsweep_128");
+        const ResidualPlan& r1 = H.res[1];
+        check(zmarch(r1, 27, 64, 4) && r1.nt == 256 && r1.sym && !r1.small, "headline_l1_residual_27_64_4_sym");
+        check(r1.pre_noise && !r1.fz && !r1.lrf && !r1.tail_noise, "headline_l1_residual_pre_noise");
+        check(H.sweep[2] == SK::QUADS && quads_lanes(3, H.sh[2].nx / 2), "headline_l2_quads_lanes");
+        check(H.sweep[3] == SK::QUADS && H.sweep[4] == SK::QUADS, "headline_l3_l4_quads");
+        check(H.tail == 5 && in_place_from(H, 5), "headline_tail_from_5");
+        check(H.res[4].small && H.res[4].tail_noise, "headline_restriction_before_tail_small");
+        check(H.res[6].kind == RK::NONE, "headline_coarsest_no_residual");
+    }
+    {  // 256^3, 6 levels: tests/test_gpu_config3.py (2 * 16 * 127 = 4,064 wide tiles: 64 x 4)
+        const Hier H = walk(3, 256, 256, 256, 6, false, 0);
+        check(H.sweep[0] == SK::ZSWEEP && zmarch(H.res[0], 7, 64, 4) && H.res[0].nt == 256 && H.res[0].fz,
+              "config3_l0_residual_7_64_4");
+        check(H.sweep[1] == SK::QUADS && zmarch(H.res[1], 27, 64, 4) && H.res[1].pre_noise, "config3_l1_quads");
+        check(H.sweep[2] == SK::QUADS && H.sweep[3] == SK::QUADS && H.tail == 4 && in_place_from(H, 4),
+              "config3_quads_then_tail");
+    }
+    {  // 24 x 20 x 12: tests/test_gpu_parity.py ROW_LENGTH_LABELS
+        const Hier H = walk(3, 24, 20, 12, 3, false, 0);
+        const ResidualPlan& r0 = H.res[0];
+        check(H.sweep[0] == SK::COLOUR, "24x20x12_l0_colour");
+        check(zmarch(r0, 7, 16, 4) && r0.nt == 64 && r0.small && r0.tail_noise && !r0.fz && !r0.lrf && !r0.pre_noise,
+              "24x20x12_l0_residual_7_16_4_small");
+        check(H.tail == 1 && in_place_from(H, 1), "24x20x12_tail_from_1");
+    }
+    {  // 96^3, 5 levels: ROW_LENGTH_LABELS
+        const Hier H = walk(3, 96, 96, 96, 5, false, 0);
+        check(H.sweep[0] == SK::COLOUR, "96_l0_colour");  // nx % 64 != 0
+        check(zmarch(H.res[0], 7, 64, 4) && !H.res[0].small, "96_l0_residual_7_64_4");
+        check(H.sweep[1] == SK::QUADS && !quads_lanes(3, H.sh[1].nx / 2), "96_l1_quads_window");
+        check(H.sweep[2] == SK::QUADS && !quads_lanes(3, H.sh[2].nx / 2), "96_l2_quads_window");
+        check(H.tail == 3 && in_place_from(H, 3), "96_tail_from_3");
+    }
+    {  // 320 x 24 x 16: ROW_LENGTH_LABELS (80-pair rows: pair passes)
+        const Hier H = walk(3, 320, 24, 16, 3, false, 0);
+        check(H.sweep[0] == SK::ZSWEEP, "320_l0_zsweep");
+        check(H.sweep[1] == SK::PAIRS && H.sh[1].nx / 2 == 80, "320_l1_pairs_80");
+        check(zmarch(H.res[1], 27, 64, 4) && H.res[1].sym && H.res[1].pre_noise, "320_l1_residual_27_64_4");
+    }
+    {  // 2D 200 x 120, 4 levels and 2D 100 x 60: ROW_LENGTH_LABELS, test_qrestrict_labels (k_residual_restrict<2,5>)
+        const Hier H = walk(2, 200, 120, 0, 4, false, 0);
+        check(H.sweep[0] == SK::RB2D, "200x120_l0_rb2d");
+        check(H.res[0].kind == RK::GATHER && H.res[0].npoints == 5 && H.res[0].cx == 0, "200x120_l0_gather_2_5");
+        check(H.sweep[1] == SK::QUADS && H.res[1].kind == RK::GATHER, "200x120_l1_quads");  // (k_quads_restrict2d)
+        check(H.tail == 2 && in_place_from(H, 2), "200x120_tail_from_2");
+        const Hier G = walk(2, 100, 60, 0, 3, false, 0);
+        check(G.sweep[0] == SK::RB2D && G.res[0].kind == RK::GATHER && G.res[0].npoints == 5, "100x60_l0_rb2d_gather");
+        check(G.tail == 1 && in_place_from(G, 1), "100x60_tail_from_1");
+    }
+    {  // FEM 512^3: tests/test_gpu_fem.py (k_jsweep_half<256>, k_jsweep_half<128>: no sym instance)
+        const Hier H = walk(3, 512, 512, 512, 7, true, 0);
+        check(H.sweep[0] == SK::JSWEEP && H.sh[0].nx / 2 == 256 && !H.res[0].sym, "fem_l0_jsweep_256_not_sym");
+        check(H.sweep[1] == SK::JSWEEP && H.sh[1].nx / 2 == 128, "fem_l1_jsweep_128");
+        check(zmarch(H.res[0], 27, 64, 4) && H.res[0].pre_noise, "fem_l0_residual_27_64_4");
+    }
+
+    // ---- boundaries ----
+    check(fine_res(7, 7, 7).kind == RK::GATHER && fine_res(7, 7, 7).cx == 0, "coarse_nx_7_gather");
+    check(zmarch(fine_res(8, 8, 8), 7, 16, 4) && fine_res(8, 8, 8).small, "coarse_nx_8_small");
+    check(zmarch(fine_res(31, 32, 32), 7, 16, 4) && fine_res(31, 32, 32).small && !fine_res(31, 32, 32).fz,
+          "coarse_nx_31_small");
+    check(zmarch(fine_res(32, 32, 32), 7, 64, 4) && !fine_res(32, 32, 32).small && fine_res(32, 32, 32).fz,
+          "coarse_nx_32_wide_tiles");
+    // 64 x 8 tiles of the coarse level: 4 * 32 * 255 = 32,640 at 512^3; 4 * 32 * 128 = 16,384 is the threshold
+    check(zmarch(fine_res(256, 256, 129), 7, 64, 8) && fine_res(256, 256, 129).nt == 512, "wide_tiles_at_threshold");
+    check(zmarch(fine_res(256, 256, 128), 7, 64, 4) && fine_res(256, 256, 128).nt == 256, "wide_tiles_below_threshold");
+
+    // ---- MGMC_DISABLE tokens: each moves the plan to the fallback its PathFlag names ----
+    {
+        const uint32_t zs = flag_of("zsweep"), pa = flag_of("pairs"), qu = flag_of("quads"), js = flag_of("jsweep"),
+                       rb = flag_of("rb2d"), zr = flag_of("zrestrict"), ta = flag_of("tail");
+        check(zs && pa && qu && js && rb && zr && ta && flag_of("no_such_path") == 0, "tokens_parse");
+        const Hier Z = walk(3, 512, 512, 512, 7, false, zs);
+        check(Z.sweep[0] == SK::COLOUR && Z.sweep[1] == SK::JSWEEP && zmarch(Z.res[0], 7, 64, 8), "token_zsweep");
+        const Hier P = walk(3, 512, 512, 512, 7, false, pa);
+        bool colour = P.sweep[0] == SK::ZSWEEP;
+        for (int l = 1; l < 7; ++l) colour = colour && P.sweep[l] == SK::COLOUR;
+        check(colour, "token_pairs");
+        const Hier Q = walk(3, 512, 512, 512, 7, false, qu);
+        check(Q.sweep[1] == SK::JSWEEP && Q.sweep[2] == SK::PAIRS && Q.sweep[3] == SK::PAIRS && Q.sweep[4] == SK::PAIRS,
+              "token_quads");
+        const Hier J = walk(3, 512, 512, 512, 7, false, js);
+        check(J.sweep[1] == SK::PAIRS && J.sweep[2] == SK::QUADS, "token_jsweep");  // 128-pair rows: no quads
+        const Hier R = walk(2, 200, 120, 0, 4, false, rb);
+        check(R.sweep[0] == SK::COLOUR && R.sweep[1] == SK::QUADS, "token_rb2d");
+        const Hier G = walk(3, 512, 512, 512, 7, false, zr);
+        bool gather = true;
+        for (int l = 0; l < 6; ++l)
+            gather = gather && G.res[l].kind == RK::GATHER && G.res[l].cx == 0 && !G.res[l].fz && !G.res[l].lrf &&
+                     !G.res[l].pre_noise && !G.res[l].tail_noise;
+        check(gather && G.res[1].sym && G.sweep[0] == SK::ZSWEEP, "token_zrestrict");
+        const Hier T = walk(3, 512, 512, 512, 7, false, ta);
+        check(T.tail == -1 && T.sweep[5] == SK::QUADS && T.sweep[6] == SK::QUADS, "token_tail");
+    }
+    return failures ? 1 : 0;
+}

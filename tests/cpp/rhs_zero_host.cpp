@@ -6,9 +6,16 @@
 #include <limits>
 #include <vector>
 
+#include "mgmc_level_plan.hpp"
 #include "mgmc_rhs_zero.hpp"
 
 using namespace mgmc_host;
+
+// ResidualPlan::fz of a 3D FD level of npoints points onto a coarse level of coarse_nx^3 cells (mgmc_level_plan.hpp)
+static bool residual_fz(int npoints, bool zrestrict, int coarse_nx) {
+    const LevelShape fine{3, npoints, 2 * coarse_nx, 2 * coarse_nx, 2 * coarse_nx, false, true, false, true};
+    return plan_residual(fine, zrestrict ? 0 : PATH_NO_ZRESTRICT, coarse_nx, coarse_nx, coarse_nx).fz;
+}
 
 static int failures = 0;
 static void check(bool ok, const char* name) {
@@ -47,7 +54,7 @@ int main() {
 
     // ---- selection ----
     // the 512^3 benchmark's level 0: z-sweep, 7-point, coarse nx 256
-    const RhsZeroOp fine{0, true, 0, 7, true, 256, 32, 0};
+    const RhsZeroOp fine{0, true, 0, residual_fz(7, true, 256), 0};
     check(rhs_zero_sweep_ok(true, fine) && rhs_zero_residual_ok(true, fine), "fine_level_zero_f");
     check(!rhs_zero_sweep_ok(false, fine) && !rhs_zero_residual_ok(false, fine), "fine_level_nonzero_f");
     RhsZeroOp o = fine;
@@ -60,16 +67,17 @@ int main() {
     o.zsweep = false;  // colour-pass kernels (MGMC_DISABLE=zsweep, nx % 64 != 0): general
     check(!rhs_zero_sweep_ok(true, o) && !rhs_zero_residual_ok(true, o), "no_zsweep");
     o = fine;
-    o.zrestrict = false;  // the gather residual kernel has no zero instance; the sweeps keep theirs
+    // MGMC_DISABLE=zrestrict: the gather residual kernel has no zero instance; the sweeps keep theirs
+    o.residual_fz = residual_fz(7, false, 256);
     check(rhs_zero_sweep_ok(true, o) && !rhs_zero_residual_ok(true, o), "no_zrestrict");
     o = fine;
-    o.npoints = 27;
+    o.residual_fz = residual_fz(27, true, 256);
     check(!rhs_zero_residual_ok(true, o), "residual_27_point");
     o = fine;
-    o.coarse_nx = 16;  // the small 16 x 4 residual kernel
+    o.residual_fz = residual_fz(7, true, 16);  // the small 16 x 4 residual kernel
     check(!rhs_zero_residual_ok(true, o), "small_residual_kernel");
     o = fine;
-    o.coarse_nx = 32;  // the smallest z-sweep level (nx 64): the 64 x 4 kernel
+    o.residual_fz = residual_fz(7, true, 32);  // the smallest z-sweep level (nx 64): the 64 x 4 kernel
     check(rhs_zero_residual_ok(true, o), "nx64_level");
     o = fine;
     o.zpre = 1;  // its spare workgroups draw a tail's noise: general

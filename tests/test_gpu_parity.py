@@ -375,7 +375,8 @@ def test_level_kernels_labels(hip_device, name, level, sweep):
     s.close()
 
 
-# the kernel instances the row length selects (mgmc_capi.hip: quads_lanes, pairs_eligible, qrestrict_threads): the
+# the kernel instances the row length selects (mgmc_level_plan.hpp: quads_lanes, pairs_eligible; mgmc_capi.hip:
+# qrestrict_threads): the
 # labels the device reports, per level.  A (key, None) entry asserts the key's absence; "sweep^" a prefix.
 ROW_LENGTH_LABELS = [
     ("3d96_5lvl", 0, {"sweep": "k_sweep_rb<3>", "residual_restrict": "k_zresrestrict<7,64,4>"}),
