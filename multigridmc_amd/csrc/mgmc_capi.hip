@@ -209,6 +209,14 @@ void launch_zsweep_t(const Level& lv, ZSweepArgs a, bool prolong, hipStream_t s,
 // z-chunk depth of a z-marching sweep: the deepest chunk (fewest prologue steps, 2 per chunk) that still
 // keeps 3/4 of the 2 x num_cu workgroup slots busy -- 512^3: 32 (plain) / 128 (post) planes, 256^3: 32 / 32.
 // Even: chunks start on odd planes (the first-colour element schedule, the coarse ring)
+// (every depth the halving below can return must be even: 24 -> 12 -> 6 is fine, 40 -> 20 -> 10 -> 5 is not)
+constexpr bool zs_depths_even(int tz) {
+    for (;; tz /= 2) {
+        if (tz < 2 || tz % 2) return false;
+        if (tz <= 8) return true;
+    }
+}
+static_assert(zs_depths_even(ZS_TZ) && zs_depths_even(ZS_TZP), "ZS_TZ / ZS_TZP: zsweep_depth would return an odd depth");
 static int zsweep_depth(const Level& lv, int ty, int tzmax) {
     const long long tiles_xy = (long long)((lv.L.nx / 2) / ZS_XP) * ((lv.L.ny - 1 + ty - 1) / ty);
     int tz = tzmax;
@@ -347,6 +355,12 @@ void launch_quads(const Level& lv, const double* xin, double* xout, const double
     // (threads per workgroup, mgmc_tuning.hpp: 2D config 2 at 1024^2: 512 10,623, 256 10,775, 128 10,883
     // samples/s; 127^3 rows 256 threads 58.3 us per 512^3 cycle against 61.6 at 512; 63^3 / 31^3 rows 128
     // threads, 512^3 launches 7.3-7.8 -> 5.6-6.3 us against 512)
+    // the workgroup is npair (T + 1) threads: at most the thread count asked for, or two rows of npair where that
+    // is less -- within k_sweep_quads' __launch_bounds__(1024) for rows of up to 512 pairs (2D: pairs_eligible's 256)
+    static_assert(tune::QUADS_NT >= 1 && tune::QUADS_NT <= 1024 && tune::QUADS_NT3 >= 1 && tune::QUADS_NT3 <= 1024 &&
+                      tune::QUADS_NT_WIDE >= 1 && tune::QUADS_NT_WIDE <= 1024 && tune::QUADS_MAXPAIR >= 1 &&
+                      tune::QUADS_MAXPAIR <= 512,
+                  "quad passes: npair (T + 1) threads must fit 1024");
     a.T = std::max(1, (dim == 3 ? (npair > 32 ? tune::QUADS_NT_WIDE : tune::QUADS_NT3) : tune::QUADS_NT) / npair - 1);
     a.nblk_y = (lv.L.ny - 1 + 2 * a.T - 1) / (2 * a.T);
     const int nt = npair * (a.T + 1);
@@ -2600,6 +2614,10 @@ int mgmc_level_kernels(const mgmc_handle* h, int level, char* out, size_t n) {
     }
     std::string text = "sweep=" + sweep;
     if (!post.empty()) text += ";post_sweep=" + post;
+    // the z-chunk depths the z-sweep launches use (zsweep_depth): plain / fused-prolongation
+    if (sweep.rfind("k_zsweep_rb7", 0) == 0)
+        text += ";tz=" + std::to_string(zsweep_depth(lv, ZS_TY, ZS_TZ)) + "/" +
+                std::to_string(zsweep_depth(lv, ZS_TYP, ZS_TZP));
     // sweeps of this level read Box-Muller pairs drawn by an earlier launch (plan_drawn_noise): the
     // restriction before the first pre-sweep and / or a tail launch
     bool by_rr = false, by_tail = false;

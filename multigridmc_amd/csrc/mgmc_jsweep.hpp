@@ -34,13 +34,14 @@
 #include <type_traits>
 
 #include "mgmc_kernels.hpp"
+#include "mgmc_level_plan.hpp"
 #include "mgmc_tuning.hpp"
 
 namespace mgmc {
 
 // NP pairs per row (nx = 2 NP); 2 NP threads (A-row pairs, B-row pairs); ring rows of stride 2 NP + 8: odd pairs [0, NP) and the guard at NP, then
 // the even block from NP + 1: its guard (position 0) first, even pair m at NP + 2 + m
-constexpr int JS_RING = 8;           // rows per plane in the LDS ring
+constexpr int JS_RING = mgmc_host::JSWEEP_RING_ROWS;  // rows per plane in the LDS ring (8)
 constexpr int JS_D = tune::JS_D;     // global loads run this many steps ahead (2 .. 4)
 static_assert(JS_D >= 2 && JS_D <= 4, "JS_D");
 
@@ -65,8 +66,8 @@ struct JSweepArgs {
 // the compiler from moving LDS accesses across it
 __device__ __forceinline__ void js_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-constexpr int JS_TAB = 322;  // Box-Muller tables in LDS: log reduction (rc, hi, lo) x 64 + cos/sin 130
-inline size_t jsweep_lds_bytes(int np) { return (size_t)(JS_RING * 3 * (2 * np + 8) + JS_TAB) * sizeof(double); }
+constexpr int JS_TAB = mgmc_host::JSWEEP_TAB_DOUBLES;  // Box-Muller tables in LDS: log reduction (rc, hi, lo) x 64 + cos/sin 130
+using mgmc_host::jsweep_lds_bytes;  // (mgmc_level_plan.hpp: the launch plan needs it on the host)
 
 // XZ: the sweep's input x is known zero (the level's first pre-sweep, mgmc_capi.hip mark_zero_inputs):
 // 1 = every x row is the constant 0.0 (the first half), 2 = the own planes' rows are (the second half;

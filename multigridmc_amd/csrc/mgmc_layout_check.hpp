@@ -41,6 +41,7 @@
 #include <vector>
 
 #include "mgmc_kernels.hpp"
+#include "mgmc_level_plan.hpp"
 
 namespace mgmc {
 
@@ -56,24 +57,10 @@ enum LayoutFamily : unsigned {
 };
 
 // launch plan of one k_jsweep_half launch (launch_jsweep): shared by the launch and the check
-struct JSweepPlan {
-    int kp, jA, nk, nsteps, spc, nchunk, nb;
-};
+// (the plan itself is host logic without HIP: mgmc_level_plan.hpp jsweep_plan_dims)
+using mgmc_host::JSweepPlan;
 inline JSweepPlan jsweep_plan(const Layout& L, bool forward, int half, int num_cu, size_t lds_bytes, int rounds) {
-    JSweepPlan p;
-    const int slots = (int)std::max<size_t>(1, (160 * 1024) / lds_bytes) * num_cu * rounds;
-    p.jA = forward ? 0 : 1;
-    p.nsteps = (L.ny - p.jA) / 2 + 1;
-    p.kp = forward ? half : 1 - half;
-    const int first = 2 - p.kp;
-    p.nk = first > L.nz - 1 ? 0 : (L.nz - 1 - first) / 2 + 1;
-    p.spc = p.nchunk = p.nb = 0;
-    if (p.nk == 0) return p;
-    const int nchunk = std::max(1, std::min(p.nsteps, slots / p.nk));
-    p.spc = (p.nsteps + nchunk - 1) / nchunk;
-    p.nchunk = (p.nsteps + p.spc - 1) / p.spc;
-    p.nb = (p.nk * p.nchunk + 7) / 8 * 8;
-    return p;
+    return mgmc_host::jsweep_plan_dims(L.ny, L.nz, forward, half, num_cu, lds_bytes, rounds);
 }
 
 // Replay of k_jsweep_half's addressing over its whole grid (host).  Every global access of the kernel

@@ -158,6 +158,36 @@ inline bool jsweep_eligible(const LevelShape& sh, uint32_t paths) {
 // (mgmc_level_kernels: quads=window)
 inline bool quads_lanes(int dim, int npair) { return dim == 3 && 64 % npair == 0 && mgmc::tune::QUADS_LANES != 0; }
 
+// ---- launch plan of one k_jsweep_half launch (launch_jsweep; replayed by mgmc_layout_check.hpp) ----
+// LDS of a workgroup: JSWEEP_RING_ROWS rows x 3 planes of 2 np + 8 doubles and the Box-Muller tables
+// (log reduction (rc, hi, lo) x 64 + cos / sin 130)
+constexpr int JSWEEP_RING_ROWS = 8;
+constexpr int JSWEEP_TAB_DOUBLES = 322;
+inline size_t jsweep_lds_bytes(int np) {
+    return (size_t)(JSWEEP_RING_ROWS * 3 * (2 * np + 8) + JSWEEP_TAB_DOUBLES) * sizeof(double);
+}
+struct JSweepPlan {
+    int kp, jA, nk, nsteps, spc, nchunk, nb;
+};
+// the half's nk own planes, each cut into nchunk chunks of spc steps: as many chunks as `rounds` rounds of the
+// resident workgroup slots (LDS-bound, 160 KB per CU) hold, at most one per step
+inline JSweepPlan jsweep_plan_dims(int ny, int nz, bool forward, int half, int num_cu, size_t lds_bytes, int rounds) {
+    JSweepPlan p;
+    const int slots = (int)std::max<size_t>(1, (160 * 1024) / lds_bytes) * num_cu * rounds;
+    p.jA = forward ? 0 : 1;
+    p.nsteps = (ny - p.jA) / 2 + 1;
+    p.kp = forward ? half : 1 - half;
+    const int first = 2 - p.kp;
+    p.nk = first > nz - 1 ? 0 : (nz - 1 - first) / 2 + 1;
+    p.spc = p.nchunk = p.nb = 0;
+    if (p.nk == 0) return p;
+    const int nchunk = std::max(1, std::min(p.nsteps, slots / p.nk));
+    p.spc = (p.nsteps + nchunk - 1) / nchunk;
+    p.nchunk = (p.nsteps + p.spc - 1) / p.spc;
+    p.nb = (p.nk * p.nchunk + 7) / 8 * 8;
+    return p;
+}
+
 // level: the level's index; tail_start: the first level k_tail can take by size (tail_start_by_size; -1 none):
 // the levels from there on keep in-place sweeps (no quads, no j-marching), so the tail can run them
 inline SweepKernel plan_sweep(const LevelShape& sh, uint32_t paths, int level, int tail_start) {

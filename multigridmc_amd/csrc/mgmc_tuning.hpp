@@ -1,10 +1,14 @@
 // mgmc_tuning.hpp -- the library's launch-shape constants, in one place.
 //
-// Every value here is bitwise-neutral: it sets tile shapes, chunk depths, thread counts and launch
-// thresholds, never an arithmetic order, so the results do not depend on it (the -m gpu suite's bitwise
-// comparisons hold at any setting -- its label assertions name the instances the values below select, e.g.
-// quads=window on every 3D quad-pass level with QUADS_LANES = 0; the layout check of mgmc_layout_check.hpp
-// covers every shape).  The values are the ones
+// Every value here is meant to be bitwise-neutral: it sets tile shapes, chunk depths, thread counts and launch
+// thresholds, never an arithmetic order, so the results must not depend on it.  tests/test_gpu_tuning.py checks
+// that: it runs the parity cases through two re-tuned builds of the library (tests/tuning_variants.py: every
+// constant below is non-default in at least one of them, asserted by tests/test_tuning_host.py) and compares
+// with the CPU oracle bit for bit, with label assertions that name the instances each variant selects.  The
+// domains that are asserted where the constant is used: ZS_TY / ZS_TYP (multiples of 4 up to 32), ZS_TZ / ZS_TZP
+// (every halving down to 8 even), JS_D (2 .. 4), ZR_SMALL_NX (>= 8), QUADS_NT* (<= 1024) and QUADS_MAXPAIR
+// (<= 512); the others are tested at the values of the two variants only.  The layout check of
+// mgmc_layout_check.hpp covers every shape.  The values are the ones
 // measured fastest on MI355X; the losing alternatives and their timings are in docs/HISTORY.md and
 // DESIGN.md 3i.  Timing experiments (scripts/build_exp.sh) build a copy of the sources with edited
 // values here; the product build has no override switches.

@@ -654,7 +654,8 @@ class MultigridMCSampler:
         and residual + restriction take it as a constant instead of reading it: same bits, a third fewer
         bytes; the key is absent otherwise; "quads": "window" on a 3D "k_sweep_quads<3>" level whose row
         length -- nx/2 pairs, not a divisor of 64 -- selects the three-load window instances instead of the
-        lane-shift ones)"""
+        lane-shift ones; "tz": "<plain>/<post>" on a level swept by k_zsweep_rb7: the z-chunk depths, in planes,
+        of the plain and of the fused-prolongation sweep launches)"""
         buf = ctypes.create_string_buffer(512)
         self._chk(self.lib.mgmc_level_kernels(self.handle, int(level), buf, 512))
         return dict(kv.split("=", 1) for kv in buf.value.decode().split(";"))

@@ -85,7 +85,39 @@ static uint32_t flag_of(const char* token) {
     return ok ? f : 0;
 }
 
-int main() {
+// "plan" mode (tests/test_tuning_host.py, compiled against a re-tuned mgmc_tuning.hpp):
+//   level_plan_host plan <nx> <ny> <nz> <nlevel> [MGMC_DISABLE list]     (nz = 0: a 2D lattice; FD prior)
+// prints one line per level,
+//   level <l> sweep <KIND> [lanes|window] [js <chunks per plane>x<steps per chunk>] residual <KIND> [np <n> cx <n> cy <n> nt <n>] [small] [sym] tail <lt>
+static int print_plan(int argc, char** argv) {
+    if (argc < 6) return 2;
+    const int nx = atoi(argv[2]), ny = atoi(argv[3]), nz = atoi(argv[4]), nlevel = atoi(argv[5]);
+    const uint32_t paths = argc > 6 && argv[6][0] ? flag_of(argv[6]) : 0;
+    if (argc > 6 && argv[6][0] && !paths) return 2;
+    const int dim = nz > 0 ? 3 : 2;
+    const Hier H = walk(dim, nx, ny, nz, nlevel, false, paths);
+    static const char* const sk[] = {"COLOUR", "FIELD", "PAIRS", "QUADS", "JSWEEP", "RB2D", "ZSWEEP"};
+    static const char* const rk[] = {"NONE", "FIELD", "GATHER", "ZMARCH"};
+    for (int l = 0; l < nlevel; ++l) {
+        const ResidualPlan& r = H.res[l];
+        std::printf("level %d sweep %s", l, sk[(int)H.sweep[l]]);
+        if (H.sweep[l] == SK::QUADS && dim == 3) std::printf(" %s", quads_lanes(dim, H.sh[l].nx / 2) ? "lanes" : "window");
+        if (H.sweep[l] == SK::JSWEEP) {  // forward sweep, first half, the 256 compute units of an MI355X
+            const JSweepPlan p = jsweep_plan_dims(H.sh[l].ny, H.sh[l].nz, true, 0, 256, jsweep_lds_bytes(H.sh[l].nx / 2),
+                                                  mgmc::tune::JS_ROUNDS);
+            std::printf(" js %dx%d", p.nchunk, p.spc);
+        }
+        std::printf(" residual %s", rk[(int)r.kind]);
+        if (r.kind == RK::ZMARCH) std::printf(" np %d cx %d cy %d nt %d", r.npoints, r.cx, r.cy, r.nt);
+        if (r.small) std::printf(" small");
+        if (r.sym) std::printf(" sym");
+        std::printf(" tail %d\n", H.tail);
+    }
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc > 1 && std::string(argv[1]) == "plan") return print_plan(argc, argv);
     {  // 512^3, 7 levels: tests/test_gpu_headline.py test_headline_kernel_instances
         const Hier H = walk(3, 512, 512, 512, 7, false, 0);
         check(H.sweep[0] == SK::ZSWEEP, "headline_l0_zsweep");
