@@ -1263,13 +1263,20 @@ Layout tail_layout(const Layout& L) {
 
 // the tail start (mgmc_level_plan.hpp tail_start) from the level shapes alone: at creation time, before any
 // level is allocated
+// (the run's length with the coarse sampler as one op, its least: a handle whose coarsest level takes separate
+// sweeps can only start its tail later -- tail_level -- and the levels in between keep their in-place sweeps)
 int tail_start_by_size(const std::vector<LevelSpec>& specs, const mgmc_config& cfg, uint32_t paths, bool field) {
     if (field || cfg.coarse_solver != MGMC_COARSE_SSOR) return -1;
-    return tail_start((int)specs.size(), paths, [&](int l, size_t* v, size_t*) {
-        const LevelSpec& sp = specs[l];
-        *v = tail_level_doubles(sp.dim, sp.n[0], sp.n[1], sp.n[2]);
-        return sp.npoints == (sp.dim == 3 ? 27 : 9);
-    });
+    return tail_start(
+        (int)specs.size(), paths,
+        [&](int l, size_t* v, size_t*) {
+            const LevelSpec& sp = specs[l];
+            *v = tail_level_doubles(sp.dim, sp.n[0], sp.n[1], sp.n[2]);
+            return sp.npoints == (sp.dim == 3 ? 27 : 9);
+        },
+        [&](int ntail) {
+            return tail_run_ops(ntail, cfg.cycle, cfg.npresmooth, cfg.npostsmooth, cfg.smoother == MGMC_SMOOTHER_SSOR);
+        });
 }
 
 // ... and of the handle's levels (x, f per level + one scratch of the largest + saved f on the rows of B):
@@ -1277,12 +1284,21 @@ int tail_start_by_size(const std::vector<LevelSpec>& specs, const mgmc_config& c
 // coarse sampler
 int tail_level(const mgmc_handle* h) {
     if (h->field_mode || h->cfg.coarse_solver != MGMC_COARSE_SSOR) return -1;
-    return tail_start((int)h->levels.size(), h->paths, [&](int l, size_t* v, size_t* extra) {
-        const Level& lv = h->levels[l];
-        *v = (size_t)tail_layout(lv.L).nstore;
-        *extra = (size_t)lv.lr.nrows;
-        return (lv.lr.m == 0 || lv.lr.small) && !lv.pingpong() && lv.spec.npoints == (lv.spec.dim == 3 ? 27 : 9);
-    });
+    const mgmc_config& c = h->cfg;
+    const Level& last = h->levels.back();  // one OP_COARSE_LDS or the sampler's sweeps (build_ops_level)
+    const int coarsest_ops = last.lds_bytes > 0 && last.lr.m == 0 ? 1 : 2 * c.ncoarsesmooth;
+    return tail_start(
+        (int)h->levels.size(), h->paths,
+        [&](int l, size_t* v, size_t* extra) {
+            const Level& lv = h->levels[l];
+            *v = (size_t)tail_layout(lv.L).nstore;
+            *extra = (size_t)lv.lr.nrows;
+            return (lv.lr.m == 0 || lv.lr.small) && !lv.pingpong() && lv.spec.npoints == (lv.spec.dim == 3 ? 27 : 9);
+        },
+        [&](int ntail) {
+            return tail_run_ops(ntail, c.cycle, c.npresmooth, c.npostsmooth, c.smoother == MGMC_SMOOTHER_SSOR,
+                                coarsest_ops);
+        });
 }
 
 void free_tails(mgmc_handle* h) {
@@ -1311,6 +1327,13 @@ int build_tails_only(mgmc_handle* h) {
     const int lt = tail_level(h);
     if (lt < 0) return MGMC_OK;
     const int L = (int)h->levels.size();
+    // (tail_start keeps both; a tail past either would write outside TailArgs::lv / TailArgs::ops)
+    if (lt < 1 || L - lt > TAIL_MAX_LEVELS)
+        return fail(h, MGMC_E_INVALID, "internal: k_tail planned for " + std::to_string(L - lt) + " levels, TailArgs holds " +
+                                           std::to_string(TAIL_MAX_LEVELS));
+    static_assert(sizeof(TailArgs::lv) / sizeof(TailLevel) == TAIL_MAX_LEVELS &&
+                      sizeof(TailArgs::ops) / sizeof(TailOp) == TAIL_MAX_OPS,
+                  "TailArgs holds TAIL_MAX_LEVELS levels and TAIL_MAX_OPS ops");
     std::vector<Op> out;
     size_t removed_before_pre = 0;
     const size_t pre_end = h->seg_end_pre;
@@ -1319,13 +1342,25 @@ int build_tails_only(mgmc_handle* h) {
             out.push_back(h->ops[q++]);
             continue;
         }
+        // the whole run -- one call of build_ops_level(lt): entered and left at level lt, nothing live below --
+        // goes into one k_tail or, if it does not fit or holds an op k_tail has not, stays as it is: decided
+        // before any of its ops is taken (k_tail loads level lt alone, so a tail may never start inside a run)
+        size_t r = q;
+        while (r < h->ops.size() && h->ops[r].level >= lt && h->ops[r].kind != OP_QOI) ++r;
+        bool ok = r - q <= (size_t)TAIL_MAX_OPS;
+        for (size_t u = q; u < r && ok; ++u) {
+            const int k = h->ops[u].kind;
+            ok = k == OP_SWEEP || k == OP_RESIDUAL_RESTRICT || k == OP_PROLONGATE || k == OP_COARSE_LDS;
+        }
+        if (!ok) {  // leave the ops as they are
+            for (size_t u = q; u < r; ++u) out.push_back(h->ops[u]);
+            q = r;
+            continue;
+        }
         TailArgs A;
         memset(&A, 0, sizeof(A));
-        size_t r = q;
-        bool ok = true;
-        for (; r < h->ops.size() && h->ops[r].level >= lt && h->ops[r].kind != OP_QOI; ++r) {
-            const Op& op = h->ops[r];
-            if (A.nops >= TAIL_MAX_OPS) { ok = false; break; }
+        for (size_t u = q; u < r; ++u) {
+            const Op& op = h->ops[u];
             TailOp& t = A.ops[A.nops++];
             t.level = op.level - lt;
             t.dir = op.direction;
@@ -1335,14 +1370,8 @@ int build_tails_only(mgmc_handle* h) {
                 case OP_SWEEP: t.kind = TAIL_SWEEP; break;
                 case OP_RESIDUAL_RESTRICT: t.kind = TAIL_RESTRICT; break;
                 case OP_PROLONGATE: t.kind = TAIL_PROLONG; break;
-                case OP_COARSE_LDS: t.kind = TAIL_COARSE; break;
-                default: ok = false;
+                default: t.kind = TAIL_COARSE; break;  // OP_COARSE_LDS
             }
-        }
-        if (!ok) {  // leave the ops as they are
-            for (size_t u = q; u < r; ++u) out.push_back(h->ops[u]);
-            q = r;
-            continue;
         }
         A.nlev = L - lt;
         int off = 0;
@@ -2577,7 +2606,11 @@ int mgmc_level_kernels(const mgmc_handle* h, int level, char* out, size_t n) {
     if (level < 0 || level >= (int)h->levels.size()) return fail(nullptr, MGMC_E_INVALID, "level out of range");
     const Level& lv = h->levels[level];
     const int dim = lv.spec.dim, np = lv.spec.npoints;
-    const int tl = tail_level(h);
+    // the tail's levels as the op list has them: a run that stayed separate launches (build_tails_only) is
+    // not reported as k_tail
+    int tl = -1;
+    for (const Op& op : h->ops)
+        if (op.kind == OP_TAIL) tl = op.level;
     const bool last = level + 1 == (int)h->levels.size();
     std::string sweep, post, res;
     if (tl >= 0 && level >= tl) {

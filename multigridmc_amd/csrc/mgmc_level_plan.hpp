@@ -265,6 +265,7 @@ inline ResidualPlan plan_residual(const LevelShape& sh, uint32_t paths, int cnx,
 }
 
 // ---- the coarsest levels' sub-cycle in one workgroup (k_tail) ----
+// (tail_start below; without a run_ops argument it plans for the default cycle)
 constexpr size_t TAIL_LDS_LIMIT = 150 * 1024;
 
 // 3D plane stride padded to sp = 8 (mod 16) doubles: k_tail's colour passes give the two halves of a
@@ -280,14 +281,45 @@ inline size_t tail_level_doubles(int dim, int nx, int ny, int nz) {
     return dim == 3 ? (size_t)tail_plane_stride(nx, ny) * (nz + 1) : (size_t)(nx + 1) * (ny + 1);
 }
 
-// smallest level lt >= 1 whose levels lt .. nlevels-1 all fit one workgroup's LDS (x, f per level + one
-// scratch of the largest + what else a level keeps there); -1 if none or only the coarsest level fits (the
-// coarse LDS kernel covers that).  level_size(l, &v, &extra): whether the tail can run level l, the doubles
-// v of one of its vectors and the doubles it keeps besides x and f
-template <class LevelSize>
-int tail_start(int nlevels, uint32_t paths, LevelSize level_size) {
+// k_tail's argument block (TailArgs, mgmc_tail.hpp) holds this many levels and this many ops; tail_start keeps
+// every tail within both
+constexpr int TAIL_MAX_LEVELS = 4;
+constexpr int TAIL_MAX_OPS = 96;
+
+// The ops of one run of the tail: one call of build_ops_level (mgmc_capi.hip) on the first of ntail >= 1 levels
+// that end at the coarsest, which is always a level > 0 and so repeats its body `cycle` times.  Per visit of a
+// level that has a coarser one: k sweeps per smoothing step (k = 2 with the SSOR smoother: forward, backward),
+// the residual + restriction, the coarser level's run, the prolongation (an op of its own on the tail's in-place
+// levels); the coarsest level is coarsest_ops ops (1: the coarse SSOR sampler in one op; otherwise its sweeps).
+//   run(coarsest) = coarsest_ops,  run(l) = cycle (k npre + 1 + run(l + 1) + 1 + k npost)
+// 4 levels: SOR 1/1 V-cycle 13, W-cycle 64, cycle = 3 183; SSOR 1/1 W-cycle 92, SSOR 2/1 W-cycle 120.
+// Exact up to 2^40 and saturated there (the counts grow like cycle^ntail).
+inline long long tail_run_ops(int ntail, int cycle, int npre, int npost, bool ssor, int coarsest_ops = 1) {
+    const long long cap = 1LL << 40;
+    const long long k = ssor ? 2 : 1;
+    long long run = std::max(coarsest_ops, 0);
+    for (int l = 1; l < ntail; ++l) {
+        const long long visit = k * std::max(npre, 0) + 2 + run + k * std::max(npost, 0);
+        run = std::min(cap, std::min<long long>(std::max(cycle, 1), 1 << 20) * visit);
+    }
+    return run;
+}
+inline bool tail_run_fits(long long run_ops) { return run_ops <= TAIL_MAX_OPS; }
+
+// smallest level lt >= 1 whose levels lt .. nlevels-1
+//  * are at most TAIL_MAX_LEVELS,
+//  * make a run of at most TAIL_MAX_OPS ops (run_ops(ntail): the ops of a run of ntail levels, tail_run_ops), and
+//  * all fit one workgroup's LDS (x, f per level + one scratch of the largest + what else a level keeps there);
+// -1 if none or only the coarsest level is left (the coarse LDS kernel covers that).  A hierarchy that is too
+// deep or a cycle that is too long for one launch starts its tail later: a run of the levels from a later start
+// is a whole call of build_ops_level too, entered and left at its first level with nothing live below.
+// level_size(l, &v, &extra): whether the tail can run level l, the doubles v of one of its vectors and the
+// doubles it keeps besides x and f
+template <class LevelSize, class RunOps>
+int tail_start(int nlevels, uint32_t paths, LevelSize level_size, RunOps run_ops) {
     if (paths & PATH_NO_TAIL) return -1;
-    for (int lt = 1; lt + 1 < nlevels; ++lt) {
+    for (int lt = std::max(1, nlevels - TAIL_MAX_LEVELS); lt + 1 < nlevels; ++lt) {
+        if (!tail_run_fits(run_ops(nlevels - lt))) continue;
         bool ok = true;
         size_t tot = 0, vmax = 0;
         for (int l = lt; l < nlevels && ok; ++l) {
@@ -299,6 +331,11 @@ int tail_start(int nlevels, uint32_t paths, LevelSize level_size) {
         if (ok && (tot + vmax) * sizeof(double) <= TAIL_LDS_LIMIT) return lt;
     }
     return -1;
+}
+// ... for the default cycle (V-cycle, one SOR pre- and post-sweep: a run of n levels is 4 n - 3 ops, 13 at most)
+template <class LevelSize>
+int tail_start(int nlevels, uint32_t paths, LevelSize level_size) {
+    return tail_start(nlevels, paths, level_size, [](int ntail) { return tail_run_ops(ntail, 1, 1, 1, false); });
 }
 
 }  // namespace mgmc_host

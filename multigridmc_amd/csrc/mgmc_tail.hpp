@@ -28,13 +28,16 @@
 // on the rows of B of every low-rank level.
 #pragma once
 #include "mgmc_kernels.hpp"
+#include "mgmc_level_plan.hpp"
 #include "mgmc_lowrank.hpp"
 
 namespace mgmc {
 
 enum TailKind { TAIL_SWEEP = 0, TAIL_RESTRICT = 1, TAIL_PROLONG = 2, TAIL_COARSE = 3 };
-constexpr int TAIL_MAX_LEVELS = 4;
-constexpr int TAIL_MAX_OPS = 96;
+// the sizes of TailArgs::lv and TailArgs::ops: set where the host-side plan, which keeps every tail within
+// them (tail_start), can see them
+using mgmc_host::TAIL_MAX_LEVELS;
+using mgmc_host::TAIL_MAX_OPS;
 
 struct TailOp {
     int kind;

@@ -30,7 +30,13 @@ struct Hier {
 // The hierarchy of an n[0] x n[1] x n[2] lattice by halving, as mgmc_create builds it: the FD prior's fine level
 // has the symmetric 5 / 7-point stencil and Galerkin levels of 9 / 27 points whose 3D stencils are
 // reflection-symmetric (fold); the FEM prior has 9 / 27 points on every level, not symmetric bit for bit.
-static Hier walk(int dim, int nx, int ny, int nz, int nlevel, bool fem, uint32_t paths) {
+// the cycle's shape, which bounds the tail by the ops of its run (tail_run_ops); the default is the V-cycle with
+// one SOR pre- and post-sweep
+struct Cycle {
+    int cycle = 1, npre = 1, npost = 1;
+    bool ssor = false;
+};
+static Hier walk(int dim, int nx, int ny, int nz, int nlevel, bool fem, uint32_t paths, Cycle cy = Cycle()) {
     Hier H;
     for (int l = 0; l < nlevel; ++l) {
         const bool galerkin = fem || l > 0;
@@ -46,11 +52,14 @@ static Hier walk(int dim, int nx, int ny, int nz, int nlevel, bool fem, uint32_t
         s.has_coarser = l + 1 < nlevel;
         H.sh.push_back(s);
     }
-    H.tail = tail_start(nlevel, paths, [&](int l, size_t* v, size_t*) {
-        const LevelShape& s = H.sh[l];
-        *v = tail_level_doubles(s.dim, s.nx, s.ny, s.nz);
-        return s.npoints == (s.dim == 3 ? 27 : 9);
-    });
+    H.tail = tail_start(
+        nlevel, paths,
+        [&](int l, size_t* v, size_t*) {
+            const LevelShape& s = H.sh[l];
+            *v = tail_level_doubles(s.dim, s.nx, s.ny, s.nz);
+            return s.npoints == (s.dim == 3 ? 27 : 9);
+        },
+        [&](int ntail) { return tail_run_ops(ntail, cy.cycle, cy.npre, cy.npost, cy.ssor); });
     for (int l = 0; l < nlevel; ++l) {
         H.sweep.push_back(plan_sweep(H.sh[l], paths, l, H.tail));
         H.res.push_back(l + 1 < nlevel ? plan_residual(H.sh[l], paths, H.sh[l + 1].nx, H.sh[l + 1].ny, H.sh[l + 1].nz)
@@ -218,6 +227,68 @@ int main(int argc, char** argv) {
         check(gather && G.res[1].sym && G.sweep[0] == SK::ZSWEEP, "token_zrestrict");
         const Hier T = walk(3, 512, 512, 512, 7, false, ta);
         check(T.tail == -1 && T.sweep[5] == SK::QUADS && T.sweep[6] == SK::QUADS, "token_tail");
+    }
+
+    // ---- the tail's limits: TailArgs (mgmc_tail.hpp) holds 4 levels and 96 ops ----
+    check(TAIL_MAX_LEVELS == 4 && TAIL_MAX_OPS == 96, "tail_limits_4_levels_96_ops");
+    {  // deep hierarchies.  By LDS size alone the 2D tails below would start at level 1, 1, 1, 2 and 4 and hold 5, 5,
+       // 6, 6 and 5 levels; in 3D the LDS limit (16^3 is the largest level that fits) stops at 4 on its own
+        struct Deep {
+            const char* name;
+            int dim, nx, ny, nz, nlevel, tail;
+        };
+        const Deep deep[] = {{"2d64_6lvl", 2, 64, 64, 0, 6, 2},         {"2d96x64_6lvl", 2, 96, 64, 0, 6, 2},
+                             {"2d128_7lvl", 2, 128, 128, 0, 7, 3},      {"2d256_8lvl", 2, 256, 256, 0, 8, 4},
+                             {"2d1024_9lvl", 2, 1024, 1024, 0, 9, 5},   {"3d32_5lvl", 3, 32, 32, 32, 5, 1},
+                             {"3d64_6lvl", 3, 64, 64, 64, 6, 2},        {"3d512_9lvl", 3, 512, 512, 512, 9, 5}};
+        for (const Deep& d : deep) {
+            const Hier H = walk(d.dim, d.nx, d.ny, d.nz, d.nlevel, false, 0);
+            check(H.tail >= 1 && d.nlevel - H.tail <= 4, std::string(d.name) + "_tail_at_most_4_levels");
+            check(H.tail == d.tail && in_place_from(H, H.tail), std::string(d.name) + "_tail_start_in_place");
+            bool before = true;  // ... and the Galerkin levels before it are not left to it
+            for (int l = 1; l < H.tail; ++l) before = before && H.sweep[l] != SK::PAIRS;
+            check(before, std::string(d.name) + "_levels_before_tail_not_pairs");
+        }
+    }
+    {  // without a cycle shape tail_start plans for the default cycle: the same depth bound
+        const Hier H = walk(2, 64, 64, 0, 6, false, 0);
+        const int t = tail_start(6, 0, [&](int l, size_t* v, size_t*) {
+            *v = tail_level_doubles(2, H.sh[l].nx, H.sh[l].ny, 0);
+            return H.sh[l].npoints == 9;
+        });
+        check(t == 2 && t == H.tail, "tail_start_default_cycle");
+    }
+    {  // the ops of one run: cycle (k npre + 1 + run(l + 1) + 1 + k npost), k = 2 with SSOR, the coarsest level 1
+        check(tail_run_ops(1, 3, 1, 1, false) == 1 && tail_run_ops(2, 1, 1, 1, false) == 5 &&
+                  tail_run_ops(4, 1, 1, 1, false) == 13 && tail_run_ops(4, 2, 1, 1, false) == 64,
+              "run_ops_sor_v_and_w");
+        check(tail_run_ops(4, 3, 1, 1, false) == 183 && !tail_run_fits(tail_run_ops(4, 3, 1, 1, false)),
+              "run_ops_sor_cycle3_183_too_long");
+        check(tail_run_ops(4, 2, 2, 1, true) == 120 && !tail_run_fits(tail_run_ops(4, 2, 2, 1, true)),
+              "run_ops_ssor_2_1_w_120_too_long");
+        check(tail_run_ops(4, 2, 1, 1, true) == 92 && tail_run_fits(tail_run_ops(4, 2, 1, 1, true)),
+              "run_ops_ssor_1_1_w_92_fits");
+        check(tail_run_ops(3, 3, 1, 1, false) == 57 && tail_run_ops(3, 2, 2, 1, true) == 52, "run_ops_3_levels");
+        check(tail_run_ops(3, 1, 0, 0, false) == 5 && tail_run_ops(2, 1, 0, 2, true, 4) == 10, "run_ops_zero_sweeps");
+        check(tail_run_fits(96) && !tail_run_fits(97), "run_fits_at_96");
+        check(tail_run_ops(4, 1 << 30, 1 << 30, 1 << 30, true) > 96 && tail_run_ops(24, 1000, 9, 9, true) > 96,
+              "run_ops_saturates_without_overflow");
+    }
+    {  // a run too long for one launch: the tail starts a level later, where a whole run fits (183 -> 57, 120 -> 52),
+       // and the level it leaves takes the quad passes; 92 ops stay in one launch from level 1
+        const Hier A = walk(3, 32, 32, 32, 5, false, 0, Cycle{3, 1, 1, false});
+        check(A.tail == 2 && in_place_from(A, 2) && A.sweep[1] == SK::QUADS, "3d32_cycle3_tail_from_2");
+        const Hier B = walk(2, 64, 64, 0, 5, false, 0, Cycle{3, 1, 1, false});
+        check(B.tail == 2 && in_place_from(B, 2) && B.sweep[1] == SK::QUADS, "2d64_cycle3_tail_from_2");
+        const Hier C = walk(3, 32, 32, 32, 5, false, 0, Cycle{2, 2, 1, true});
+        check(C.tail == 2 && in_place_from(C, 2) && C.sweep[1] == SK::QUADS, "3d32_ssor_2_1_w_tail_from_2");
+        const Hier D = walk(3, 32, 32, 32, 5, false, 0, Cycle{2, 1, 1, true});
+        check(D.tail == 1 && in_place_from(D, 1) && D.sweep[1] == SK::PAIRS, "3d32_ssor_1_1_w_tail_from_1");
+        // no two levels' run fits (100 + 2 + 1 + 1 ops): no tail, every level on its own kernels
+        const Hier E = walk(3, 32, 32, 32, 5, false, 0, Cycle{1, 100, 1, false});
+        check(E.tail == -1 && E.sweep[3] == SK::QUADS, "3d32_100_presweeps_no_tail");
+        const Hier F = walk(3, 32, 32, 32, 5, false, 0, Cycle{1, 0, 0, false});
+        check(F.tail == 1 && in_place_from(F, 1), "3d32_no_sweeps_tail_from_1");
     }
     return failures ? 1 : 0;
 }
