@@ -1690,6 +1690,27 @@ orc_handle* orc_create_csr(const orc_params* q, int mode, uint64_t seed, int64_t
     return h;
 }
 
+// A constant 3^d stencil (27 doubles in sidx order; a 2D stencil in the first 9) as the fine operator: its
+// truncation on the lattice (stencil_csr; zero coefficients are no entries), Galerkin levels by the oracle's own
+// SpGEMM (q->galerkin as for orc_create_fd).  The device builds such an operator as a stencil hierarchy
+// (mgmc_create_stencil_batch), so reflection-symmetric 27-point levels fold here too (orc_set_no_fold honoured).
+orc_handle* orc_create_stencil(const orc_params* q, int mode, uint64_t seed, uint64_t chain, const double* st) {
+    if (!st || q->dim < 2) return nullptr;
+    orc_handle* h = new orc_handle();
+    h->ctx.mode = (Mode)mode;
+    h->ctx.rng.seed(seed);
+    h->ctx.seed = seed;
+    h->ctx.chain = chain;
+    const Lattice lat = make_lattice(q);
+    double fine[27];
+    for (int k = 0; k < 27; ++k) fine[k] = k < (q->dim == 3 ? 27 : 9) ? st[k] : 0.0;
+    CSR A = stencil_csr(lat, fine);
+    h->mg.reset(new MGMC(&h->ctx, to_params(q), lat, std::move(A), nullptr, /*stencil_hierarchy=*/true));
+    h->f.assign(h->mg->x_ell[0].size(), 0.0);
+    h->x.assign(h->mg->x_ell[0].size(), 0.0);
+    return h;
+}
+
 void orc_destroy(orc_handle* h) { delete h; }
 
 // worker threads of the row-parallel loops (see g_threads); results do not depend on it

@@ -26,6 +26,7 @@ orc_handle* orc_create_fd(const orc_params* q, int mode, uint64_t seed, uint64_t
 orc_handle* orc_create_fem(const orc_params* q, int mode, uint64_t seed, uint64_t chain, const double* override_st);
 orc_handle* orc_create_csr(const orc_params* q, int mode, uint64_t seed, int64_t nrow, const int64_t* rowptr,
                            const int32_t* col, const double* val);
+orc_handle* orc_create_stencil(const orc_params* q, int mode, uint64_t seed, uint64_t chain, const double* st);
 void orc_destroy(orc_handle* h);
 void orc_set_chol_blocked(int on);
 int64_t orc_ndof(orc_handle* h, int level);
@@ -238,6 +239,29 @@ int main() {
             }
         orc_params pc = params(2, 16, 3, 1, 0, 0);
         orc_handle* h = orc_create_csr(&pc, mode, 3ull, n * n, rp.data(), col.data(), val.data());
+        if (h) {
+            exercise(h, false);
+            orc_destroy(h);
+        }
+        // user stencils through orc_create_stencil: a reflection-symmetric 27-point one (fold levels, full SpGEMM
+        // and the stencil-mode RAP) and a 9-point one without symmetry given as its first 9 entries
+        double s27[27], s9[9];
+        for (int t = 0; t < 27; ++t) {
+            const int n1 = (t % 3 != 1) + ((t / 3) % 3 != 1) + (t / 9 != 1);
+            s27[t] = n1 == 0 ? 24.0 : -1.0 / (1 << (n1 - 1)) * (t / 9 != 1 ? 1.5 : 1.0);
+        }
+        for (int t = 0; t < 9; ++t) s9[t] = t == 4 ? 11.0 : -(0.25 + 0.1 * t);
+        for (int galerkin = 0; galerkin <= 1; ++galerkin) {
+            orc_params ps = params(3, 16, 3, 1, 1, 0);
+            ps.galerkin = galerkin;
+            h = orc_create_stencil(&ps, mode, 5ull, 1, s27);
+            if (h) {
+                exercise(h, false);
+                orc_destroy(h);
+            }
+        }
+        const orc_params ps2 = params(2, 32, 3, 2, 0, 0);
+        h = orc_create_stencil(&ps2, mode, 5ull, 0, s9);
         if (h) {
             exercise(h, false);
             orc_destroy(h);

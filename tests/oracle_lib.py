@@ -43,6 +43,7 @@ def lib():
             "orc_create_fem": (c_void_p, [POINTER(OrcParams), c_int, c_uint64, c_uint64, _DP]),
             "orc_create_csr": (c_void_p, [POINTER(OrcParams), c_int, c_uint64, c_int64, POINTER(c_int64),
                                           POINTER(c_int32), _DP]),
+            "orc_create_stencil": (c_void_p, [POINTER(OrcParams), c_int, c_uint64, c_uint64, _DP]),
             "orc_destroy": (None, [c_void_p]),
             "orc_set_threads": (None, [c_int]),
             "orc_set_chol_blocked": (None, [c_int]),
@@ -178,6 +179,23 @@ class Oracle:
                                  dp(val))
         if not h:
             raise ValueError("the multicolour order needs a 2D / 3D lattice")
+        return cls(h, p)
+
+    @classmethod
+    def stencil(cls, shape, mg, st, mode=MULTICOLOUR, seed=5418513, chain=0):
+        """A constant 3^d stencil (27 / 9 entries in mgmc_level_desc.stencil order) as the fine operator, truncated
+        on the lattice; the oracle's own Galerkin levels (full SpGEMM up to 2^18 fine unknowns, above that the
+        stencil-mode RAP of fd_own), reflection-symmetric 27-point levels folded as on the device's stencil path
+        (mgmc_create_stencil_batch) unless set_no_fold."""
+        big = int(np.prod([n - 1 for n in shape])) > (1 << 18)
+        p = params_struct(shape, mg, 0.0, 1 if big else 0)
+        full = np.zeros(27)
+        st = np.asarray(st, dtype=np.float64)
+        assert st.shape == (27 if len(shape) == 3 else 9,)
+        full[:len(st)] = st
+        h = lib().orc_create_stencil(ctypes.byref(p), mode, seed, chain, dp(full))
+        if not h:
+            raise ValueError("a stencil needs a 2D / 3D lattice")
         return cls(h, p)
 
     def __del__(self):
