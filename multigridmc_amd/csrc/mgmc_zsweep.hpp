@@ -77,6 +77,9 @@ struct ZItem {
 struct RunE0 {
     int value;
 };
+struct BranchE0 {
+    int value;
+};
 
 // threads of a TY-row tile: TY/2 core waves + 2 halo waves, rounded up to a multiple of 4 waves
 constexpr int zs_threads(int TY) { return 256 * ((TY / 2 + 2 + 3) / 4); }
@@ -216,7 +219,8 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MINW)))
     // pairs, so every element choice in it is a compile-time constant: no selects, and pair loads
     // and stores stay 16-byte accesses (the two copies execute the same sequence of barriers).  The
     // fused-prolongation sweep keeps one copy with wave-uniform selects (its registers are the
-    // binding limit: 2 workgroups of 12 waves per CU need <= 80 VGPRs).
+    // binding limit: 2 workgroups of 12 waves per CU need <= 80 VGPRs); its zero-f instance branches
+    // per step to colour sections compiled for either element instead (BranchE0 below).
     const int E0 = __builtin_amdgcn_readfirstlane(((wpar ^ (k0 - 1)) & 1) == fc ? 0 : 1);
     const int E0d = __builtin_amdgcn_readfirstlane(((wpar ^ k1) & 1) == fc ? 0 : 1);
     // the odd / even element is an interior vertex (per lane; boundary vertices are never written)
@@ -416,8 +420,11 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MINW)))
     // (its slot held plane (p-1)/2, last read at step p-1).
     double2 z = make_double2(0.0, 0.0);
     double fb = 0.0;  // first-colour value below (plane p-2) at the second-colour position of p-1
-    // E0c: std::integral_constant (E0 known at compile time in this copy of the march) or RunE0 (a
-    // wave-uniform run-time value: the fused-prolongation sweep, one copy, fewer registers)
+    // E0c: std::integral_constant (E0 known at compile time in this copy of the march), RunE0 (a
+    // wave-uniform run-time value: the fused-prolongation sweep, one copy, fewer registers) or BranchE0 (the
+    // zero-f fused-prolongation sweep: one copy of the march, deposits and noise shared, but each step's two
+    // colour sections compiled per element under a wave-uniform branch -- no selects, 68 VGPRs; two whole
+    // copies of that march need 80 VGPRs and spill 7)
     // DNc: a downward march (zpairs, plain sweep only): steps p = k1, k1 - 1, ..., k0 - 1; deposit x(p-1)
     // into the slot of plane p+3, issue x(p-2) and f(p-1); first colour on p, second colour on p+1, whose
     // below value (plane p, written by this step's first colour) comes from LDS and whose above value
@@ -429,9 +436,20 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MINW)))
         auto step = [&](int p, auto ODDc, double2& fcur, double2& fnxt, double pk_in, double& pk_out)
                         __attribute__((always_inline)) {
             constexpr bool odd_step = decltype(ODDc)::value;
-            const int e = odd_step ? 1 - E0c_v : E0c_v;  // first-colour element on plane p
-            const int o1 = t.lds + e * WP, o2 = t.lds + (1 - e) * WP;
-            const bool inf = e ? in1 : in0;  // (compile-time choice)
+            const int e_step = odd_step ? 1 - E0c_v : E0c_v;  // first-colour element on plane p
+            // the two colour sections below take the element as ec.value: a constant (this copy of the march
+            // is compiled for E0), a run-time value (RunE0: selects), or (BranchE0) a constant again, under a
+            // wave-uniform branch over the section compiled for either element
+            auto with_e = [&](auto&& section) __attribute__((always_inline)) {
+                if constexpr (std::is_same<decltype(E0c), BranchE0>::value) {
+                    if (e_step) section(std::integral_constant<int, 1>{});
+                    else section(std::integral_constant<int, 0>{});
+                } else if constexpr (std::is_same<decltype(E0c), RunE0>::value) {
+                    section(RunE0{e_step});
+                } else {
+                    section(std::integral_constant<int, odd_step ? 1 - decltype(E0c)::value : decltype(E0c)::value>{});
+                }
+            };
             // p even on even steps: plane p+1 odd (register set 1), p+3 too
             using Bp = std::integral_constant<int, odd_step ? 0 : 1>;
             deposit_x(p + dz, std::integral_constant<int, DN ? -1 : (odd_step ? 0 : 1)>{}, Bp{});
@@ -455,39 +473,50 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MINW)))
                 double2 fv = make_double2(0.0, 0.0);  // (FZ: the constant)
                 if constexpr (!FZ) fv = fcur;
                 if constexpr (LRF) fv = lr_rhs_pair(fv, lre);
-                if (inf) {
-                    const double res = row_sum(p, o1, e, xs[slot(p - 1) * PS + o1]);
-                    const double crhs = fma(sd, e ? z.y : z.x, e ? fv.y : fv.x);
-                    double* s0 = xs + slot(p) * PS;
-                    s0[o1] = fma(wd, crhs - res, s0[o1]);
-                }
-                pk_out = fma(sd, e ? z.x : z.y, e ? fv.x : fv.y);
+                with_e([&](auto ec) __attribute__((always_inline)) {
+                    const int e = ec.value;
+                    const int o1 = t.lds + e * WP;
+                    const bool inf = e ? in1 : in0;  // (compile-time choice)
+                    if (inf) {
+                        const double res = row_sum(p, o1, e, xs[slot(p - 1) * PS + o1]);
+                        const double crhs = fma(sd, e ? z.y : z.x, e ? fv.y : fv.x);
+                        double* s0 = xs + slot(p) * PS;
+                        s0[o1] = fma(wd, crhs - res, s0[o1]);
+                    }
+                    pk_out = fma(sd, e ? z.x : z.y, e ? fv.x : fv.y);
+                });
             }
             if constexpr (PF2 && !FZ) fcur = load_f(p + 2);  // this step's f is used up: the registers take f(p+2)
             __syncthreads();
             // second colour on plane k = p-1 (DN: p+1; its element is e: the parity flips with the plane)
             const int k = p - dz;
             if (core_wave) {
-                const bool own = k >= k0 && k < k1;  // a core plane of this tile (interior)
-                const double* s0 = xs + slot(k) * PS;
-                const double fv = s0[o2];             // final first-colour value
-                if (own && rowin) {
-                    double sv = s0[o1];
-                    if (inf) {
-                        // DN: below = plane p (this step's first colour, LDS), above = plane p+2 (fb); the
-                        // slot of p+2 takes the next step's deposit, so it is not read here
-                        const double res = DN ? row_sum_ba(k, o1, e, xs[slot(p) * PS + o1], fb) : row_sum(k, o1, e, fb);
-                        sv = fma(wd, pk_in - res, sv);
+                with_e([&](auto ec) __attribute__((always_inline)) {
+                    const int e = ec.value;
+                    const int o1 = t.lds + e * WP, o2 = t.lds + (1 - e) * WP;
+                    const bool inf = e ? in1 : in0;
+                    const bool own = k >= k0 && k < k1;  // a core plane of this tile (interior)
+                    const double* s0 = xs + slot(k) * PS;
+                    const double fv = s0[o2];             // final first-colour value
+                    if (own && rowin) {
+                        double sv = s0[o1];
+                        if (inf) {
+                            // DN: below = plane p (this step's first colour, LDS), above = plane p+2 (fb); the
+                            // slot of p+2 takes the next step's deposit, so it is not read here
+                            const double res =
+                                DN ? row_sum_ba(k, o1, e, xs[slot(p) * PS + o1], fb) : row_sum(k, o1, e, fb);
+                            sv = fma(wd, pk_in - res, sv);
+                        }
+                        double* dst = a.xout + (long long)k * L.sp + t.goff;
+                        // (x, y) = (odd, even) element; the second colour is element e here
+                        const double2 out = e ? make_double2(fv, sv) : make_double2(sv, fv);
+                        // streaming store: keep the write stream out of L2 (plain stores: pre-sweep 0.641 ->
+                        // 0.673 ms)
+                        __builtin_nontemporal_store(out.x, dst);
+                        __builtin_nontemporal_store(out.y, dst + 1);
                     }
-                    double* dst = a.xout + (long long)k * L.sp + t.goff;
-                    // (x, y) = (odd, even) element; the second colour is element e here
-                    const double2 out = e ? make_double2(fv, sv) : make_double2(sv, fv);
-                    // streaming store: keep the write stream out of L2 (plain stores: pre-sweep 0.641 ->
-                    // 0.673 ms)
-                    __builtin_nontemporal_store(out.x, dst);
-                    __builtin_nontemporal_store(out.y, dst + 1);
-                }
-                fb = fv;  // the next step's value below (UP) / above (DN) at its second-colour position
+                    fb = fv;  // the next step's value below (UP) / above (DN) at its second-colour position
+                });
             }
             if (active_wave && interior_plane(p + dz)) z = noise(p + dz);
         };
@@ -552,7 +581,8 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MINW)))
     }
     issue_x(k0, B1{});
     if constexpr (PF2) issue_x(k0 + 1, B0{});
-    if (PROLONG) run(RunE0{E0}, UP{});
+    if (PROLONG && FZ) run(BranchE0{E0}, UP{});
+    else if (PROLONG) run(RunE0{E0}, UP{});
     else if (E0) run(std::integral_constant<int, 1>{}, UP{});  // wave-uniform branch
     else run(std::integral_constant<int, 0>{}, UP{});
 }

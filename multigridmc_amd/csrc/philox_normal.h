@@ -88,6 +88,19 @@ MGMC_HD uint64_t as_bits(double d) {
 // u1 = 2 - v in (0,1] and u2 = v - 1 in [0,1) -- both subtractions are exact.
 MGMC_HD uint64_t bits52(uint32_t a, uint32_t b) { return ((uint64_t)a << 20) | (uint64_t)(b >> 12); }
 
+// the double 1.m with m = bits52(a, b).  On the device the two words are funnel shifts of (a : b) and of
+// (0x3ff : a) by 12 (v_alignbit_b32 each) -- the same 64 bits as the shift and the two ors of the host form:
+// low word (a << 20) | (b >> 12), high word (0x3ff << 20) | (a >> 12).
+MGMC_HD double unit_double(uint32_t a, uint32_t b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t lo = __builtin_amdgcn_alignbit(a, b, 12);
+    const uint32_t hi = __builtin_amdgcn_alignbit(0x3ffu, a, 12);
+    return as_double(((uint64_t)hi << 32) | lo);
+#else
+    return as_double(0x3ff0000000000000ull | bits52(a, b));
+#endif
+}
+
 // natural log of u in [2^-52, 1], division free: u = 2^e m, m in [1,2), table point
 // rc_i ~ 1/m (top 6 mantissa bits), r = m rc_i - 1 (|r| < 1/128, one fma), log1p(r) by a
 // degree-8 polynomial, plus the tabulated -log(rc_i) = hi + lo (log_table.h).  Absolute error
@@ -152,7 +165,13 @@ MGMC_HD double sqrt_rad(double x) {
     g = fma(d, h, g);
     d = fma(-g, g, x);
     g = fma(d, h, g);
-    return x > 0.0 ? g : 0.0;
+    // x > 0 ? g : 0 as one v_max_f64 (IEEE maxNum: a NaN operand gives the other one).  For the x the caller
+    // passes (-2 log u, u in (0, 1]: +0, or >= 2^-52; a negative x only by the log's last-bit error at u = 1):
+    //   x > 0: y, g, h are finite and positive, g = sqrt(x) > 0, max(g, +0) = g;
+    //   x = +0 / -0: y = +inf / -inf, g = 0 * inf = NaN and stays NaN through the fma chain, max(NaN, +0) = +0;
+    //   x < 0: y = NaN, so g = NaN, max(NaN, +0) = +0.
+    // The select gave g, +0, +0 in the three cases: the same bits.
+    return __builtin_fmax(g, 0.0);
 #else
     return x > 0.0 ? sqrt(x) : 0.0;
 #endif
@@ -161,8 +180,8 @@ MGMC_HD double sqrt_rad(double x) {
 // Box-Muller pair from one Philox block: (z_cos, z_sin)
 MGMC_HD void normal_pair_t(const Philox4& r, double* z0, double* z1, const double* rct, const double* hit,
                            const double* lot, const double* sct) {
-    const double v1 = as_double(0x3ff0000000000000ull | bits52(r.v[0], r.v[1]));
-    const double v2 = as_double(0x3ff0000000000000ull | bits52(r.v[2], r.v[3]));
+    const double v1 = unit_double(r.v[0], r.v[1]);
+    const double v2 = unit_double(r.v[2], r.v[3]);
     const double u1 = 2.0 - v1;  // (0,1]
     const double u2 = v2 - 1.0;  // [0,1)
     const double rad = sqrt_rad(-2.0 * log_unit(u1, rct, hit, lot));
