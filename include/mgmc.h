@@ -161,6 +161,19 @@ int mgmc_csr_colour_scheme(const mgmc_config* cfg, int level, int64_t nrow, cons
 int mgmc_stencil_of_csr(const mgmc_config* cfg, int64_t nrow, const int64_t* rowptr, const int32_t* col,
                         const double* val, double* stencil);
 
+/* A constant stencil plus a diagonal field (ABI 5; host only): MGMC_OK and stencil[27] (offset order of
+ * mgmc_level_desc, stencil[13] = 0.0) if the CSR on cfg's 3D lattice is a constant, symmetric axis-neighbour
+ * stencil truncated at the boundary plus an arbitrary positive finite diagonal: every stored off-diagonal is an
+ * axis neighbour, all entries of one offset are bitwise equal, -x/+x, -y/+y, -z/+z are equal, no interior
+ * coupling is missing -- the matrix of ShiftedLaplaceFDOperator with any correlation-length model (kappa^2
+ * enters its diagonal only).  MGMC_E_UNSUPPORTED otherwise; same argument validation as mgmc_create_csr.
+ * mgmc_create_csr runs this check on its fine matrix: a level that passes (a constant diagonal included) and
+ * has the z-sweep's shape (3D, nx a multiple of 64, a coarser level) is swept and restricted by the z-marching
+ * kernels with the diagonal streamed per vertex (mgmc_level_kernels: diag=field), bitwise equal to the field
+ * kernels it replaces; MGMC_DISABLE=zsweep keeps those. */
+int mgmc_vardiag_of_csr(const mgmc_config* cfg, int64_t nrow, const int64_t* rowptr, const int32_t* col,
+                        const double* val, double* stencil);
+
 /* Host-side bounds check of one level's padded layout (ABI 5; host only; mgmc_create runs it on
  * every level of every handle).  families: MGMC_LAYOUT_* bits of the kernels that address the level;
  * reach: 1 (3^d couplings) or 2 (the squared FD operator's levels); zrestrict_cx: coarse points per
@@ -220,7 +233,7 @@ int mgmc_nchains(const mgmc_handle* h);
 int mgmc_destroy(mgmc_handle* h);
 int mgmc_level_desc_get(const mgmc_handle* h, int level, mgmc_level_desc* out);
 /* The kernels this handle runs on a level (ABI 5), as text "sweep=<kernel>[;post_sweep=<kernel>]
- * [;noise=<source>][;residual_restrict=<kernel>][;rhs=zero][;lowrank=<path>][;quads=window]", the keys in this
+ * [;noise=<source>][;residual_restrict=<kernel>][;rhs=zero][;diag=field][;lowrank=<path>][;quads=window]", the keys in this
  * order -- for labels (bench.py) and profiles;
  * quads=window: a 3D k_sweep_quads<3> level whose rows (nx/2 pairs, not a divisor of 64) run the three-load
  * window instances; without the key such a level runs the lane-shift instances;
@@ -230,6 +243,10 @@ int mgmc_level_desc_get(const mgmc_handle* h, int level, mgmc_level_desc* out);
  * mgmc_set_rhs / mgmc_apply of zeros; -0.0, denormals and NaN are not zero) and the cycle's z-marching
  * sweeps and residual + restriction named above run their instances that take it as a constant instead of
  * reading it -- same bits; absent on every other level, with a low-rank part, and on the general kernels;
+ * diag=field, on level 0 of a matrix handle only: the fine matrix is a constant stencil plus a diagonal field
+ * (mgmc_vardiag_of_csr) and the level runs k_zsweep_rb7<...,VD> and, unless MGMC_DISABLE=zrestrict,
+ * k_zresrestrict<7,64,4|8>, their instances that stream the diagonal per vertex; such a level has no post_sweep
+ * (the prolongation is a launch of its own) and never rhs=zero; mgmc_level_desc.varcoef stays 1;
  * <path> on a posterior level: small | rows | dense | dense,rhs_inplace */
 int mgmc_level_kernels(const mgmc_handle* h, int level, char* out, size_t n);
 

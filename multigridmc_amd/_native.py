@@ -89,6 +89,8 @@ SIGNATURES = [
     ("mgmc_check_layout", c_int, [c_int, POINTER(c_int), c_int, ctypes.c_uint, c_int, c_int]),
     ("mgmc_stencil_of_csr", c_int, [POINTER(MgmcConfig), c_int64, POINTER(c_int64), POINTER(ctypes.c_int32), _DP,
                                     _DP]),
+    ("mgmc_vardiag_of_csr", c_int, [POINTER(MgmcConfig), c_int64, POINTER(c_int64), POINTER(ctypes.c_int32), _DP,
+                                    _DP]),
     ("mgmc_create_stencil_batch", c_int, [POINTER(MgmcConfig), _DP, c_int, c_uint64, c_uint64, c_int,
                                           POINTER(c_void_p)]),
     ("mgmc_create_batch", c_int, [POINTER(MgmcConfig), c_int, c_uint64, c_uint64, c_int, POINTER(c_void_p)]),

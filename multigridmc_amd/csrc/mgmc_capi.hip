@@ -258,6 +258,24 @@ void launch_zsweep(const Level& lv, const double* xin, double* xout, const doubl
     a.G = g0;
     a.G.colour = (direction == MGMC_FORWARD) ? 0 : 1;
     a.zpairs = 0;
+    a.dg = a.wdv = a.sdv = nullptr;
+    if (lv.vardiag()) {
+        // the VD instance (plain sweep only: push_sweep folds no prolongation into it, mark_rhs_zero leaves the
+        // level alone, the low-rank setup keeps its right-hand side out of place).  The fused-prolongation
+        // sweep's tile: three more pair streams do not fit the plain instance's 80 VGPRs either (mgmc_tuning.hpp)
+        a.dg = lv.vd[0];
+        a.wdv = lv.vd[1];
+        a.sdv = lv.vd[2];
+        a.tz = zsweep_depth(lv, ZS_TYP, ZS_TZ);
+        a.zpairs = 1;
+        a.ntx = (lv.L.nx / 2) / ZS_XP;
+        a.nty = (lv.L.ny - 1 + ZS_TYP - 1) / ZS_TYP;
+        a.ntz = (lv.L.nz - 1 + a.tz - 1) / a.tz;
+        const int ntiles = a.ntx * a.nty * ((a.ntz + 1) / 2 * 2);
+        hipLaunchKernelGGL((k_zsweep_rb7<ZS_XP, ZS_TYP, ZS_NTP, 0, 1, false, false, true>),
+                           dim3((ntiles + 7) / 8 * 8, 1, nch), dim3(ZS_NTP), zsweep_lds_bytes(ZS_XP, ZS_TYP, false), s, a);
+        return;
+    }
     if (coarse) {  // fused-prolongation sweep
         a.tz = zsweep_depth(lv, ZS_TYP, ZS_TZP);
         launch_zsweep_t<ZS_XP, ZS_TYP, ZS_NTP, ZS_MINWP>(lv, a, true, s, nch, fzero);
@@ -531,13 +549,14 @@ void launch_coarse_lds(const Level& lv, const GibbsArg& g, int nsweeps, hipStrea
 }
 
 
-template <int NPTS, int CX, int CY, int NT, bool SYM = false, bool LRF = false, bool FZ = false>
+template <int NPTS, int CX, int CY, int NT, bool SYM = false, bool LRF = false, bool FZ = false, bool VD = false>
 void launch_zresrestrict_t(const Level& lf, const Level& lc, const double* x, const double* f, double* fc, double* xc,
                            hipStream_t s, int nch, const TailNoiseLaunch* tn = nullptr, const LRRhsArg* lr = nullptr,
                            const PreNoiseLaunch* pn = nullptr) {
     ZRestrictArgs a;
     memset(&a, 0, sizeof(a));
     if (LRF) a.lr = *lr;
+    if (VD) a.dg = lf.vd[0];  // the level's diagonal vector (ResidualPlan::vardiag)
     if (pn) {  // (one chain: nch == 1)
         a.pn = pn->job;
         a.key = pn->key;
@@ -606,7 +625,7 @@ void launch_zresrestrict_t(const Level& lf, const Level& lc, const double* x, co
                            zrestrict_lds_bytes(CX, CY), s, a);
         return;
     }
-    hipLaunchKernelGGL((k_zresrestrict<NPTS, CX, CY, NT, false, SYM, LRF, FZ>), dim3(nb, 1, nch), dim3(NT),
+    hipLaunchKernelGGL((k_zresrestrict<NPTS, CX, CY, NT, false, SYM, LRF, FZ, VD>), dim3(nb, 1, nch), dim3(NT),
                        zrestrict_lds_bytes(CX, CY), s, a);
 }
 
@@ -648,7 +667,10 @@ void launch_residual_restrict(const Level& lf, const Level& lc, const double* x,
         case ResidualKind::ZMARCH: {
             const bool wide = p.nt == 512;  // 64 x 8 coarse points per workgroup (7-point levels)
             if (skip_xc) xc = nullptr;
-            if (lr) {
+            if (p.vardiag) {  // (no LRF / FZ / tail-noise instances: the plan has lrf, fz, tail_noise false)
+                if (wide) launch_zresrestrict_t<7, 64, 8, 512, false, false, false, true>(lf, lc, x, f, fc, xc, s, nch);
+                else launch_zresrestrict_t<7, 64, 4, 256, false, false, false, true>(lf, lc, x, f, fc, xc, s, nch);
+            } else if (lr) {
                 if (wide) launch_zresrestrict_t<7, 64, 8, 512, false, true>(lf, lc, x, f, fc, xc, s, nch, nullptr, lr);
                 else launch_zresrestrict_t<7, 64, 4, 256, false, true>(lf, lc, x, f, fc, xc, s, nch, nullptr, lr);
             } else if (fzero && p.fz) {
@@ -1103,7 +1125,8 @@ void push_sweep(mgmc_handle* h, std::vector<int>& cur, int level, int direction,
     // fused prolongation on z-sweep levels (the 2D red-black kernel does not fold it: its staging
     // becomes a longer latency chain, 2D 1024^2 cycle 0.1292-0.1305 -> 0.1306-0.1316 ms against the
     // separate k_prolongate_pairs launch, measured in round 1)
-    const bool fold = lv.sweep == SweepKernel::ZSWEEP && !(h->paths & PATH_NO_FUSE_PROLONG);
+    // (a variable-diagonal level has no fused-prolongation instance: the separate prolongation op below)
+    const bool fold = lv.sweep == SweepKernel::ZSWEEP && !lv.vardiag() && !(h->paths & PATH_NO_FUSE_PROLONG);
     if (lv.pingpong() && pending_prolong && !fold) {
         h->ops.push_back({OP_PROLONGATE, level, 0, 0, 0});
         h->ops.back().src = cur[level];
@@ -1616,7 +1639,8 @@ void mark_zero_inputs(mgmc_handle* h) {
 // (the conditions themselves: mgmc_rhs_zero.hpp, host-only and tested on the CPU)
 static RhsZeroOp rhs_zero_op(const mgmc_handle* h, const Op& op) {
     const Level& lv = h->levels[op.level];
-    return RhsZeroOp{op.level, lv.sweep == SweepKernel::ZSWEEP, lv.lr.m, lv.res.fz, op.zpre};
+    // (a variable-diagonal level has no FZ instances: never marked)
+    return RhsZeroOp{op.level, lv.sweep == SweepKernel::ZSWEEP && !lv.vardiag(), lv.lr.m, lv.res.fz, op.zpre};
 }
 // returns whether any op's mark changed (the graphs embed the kernel choice: the caller rebuilds them)
 bool mark_rhs_zero(mgmc_handle* h) {
@@ -2194,13 +2218,58 @@ static std::string check_level_layout_of(const mgmc_handle* h, int l) {
     if (lv.sweep == SweepKernel::RB2D) fam |= LF_RB2D;
     const int cx = lv.res.cx;  // (z-marching residual + restriction only)
     if (cx) fam |= LF_ZRESTRICT;
-    if (l > 0 && h->levels[l - 1].sweep == SweepKernel::ZSWEEP) fam |= LF_ZSWEEP_C;
+    // (the fused prolongation's reads on the coarse level: not below a variable-diagonal level, which has none)
+    if (l > 0 && h->levels[l - 1].sweep == SweepKernel::ZSWEEP && !h->levels[l - 1].vardiag()) fam |= LF_ZSWEEP_C;
     if (lv.sweep == SweepKernel::JSWEEP) fam |= LF_JSWEEP;
     if (qrestrict_ok(h, l)) fam |= LF_QRESTRICT;
     const int reach = lv.field && (lv.F.scheme == 9 || lv.F.scheme == 27) ? 2 : 1;
     std::string e = check_level_layout(lv.L, fam, reach, cx);
     if (e.empty() && lv.sweep == SweepKernel::JSWEEP) e = jsweep_grid_check_level(lv.L, lv.num_cu);
     return e;
+}
+
+// The check of mgmc_vardiag_of_csr on a matrix whose shape is validated (check_csr_shape): "" and the stencil
+// (offset order of mgmc_level_desc, centre 0.0), or why the matrix is not a constant symmetric axis-neighbour
+// stencil truncated at the boundary plus a positive finite diagonal.  No entry is indexed by a column value.
+static std::string vardiag_of_csr(const mgmc_config& cfg, int64_t nrow, const int64_t* rowptr, const int32_t* col,
+                                  const double* val, double* stencil) {
+    if (cfg.dim != 3) return "not a 3D lattice";
+    const int64_t nxi = cfg.nx - 1, nyi = cfg.ny - 1, nzi = cfg.nz - 1;
+    static const int off[7][3] = {{0, 0, -1}, {0, -1, 0}, {-1, 0, 0}, {0, 0, 0}, {1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+    static const int slot[7] = {4, 10, 12, 13, 14, 16, 22};
+    uint64_t bits[7] = {0};
+    bool have[7] = {false};
+    for (int64_t r = 0; r < nrow; ++r) {
+        const int64_t ri = r % nxi + 1, rj = (r / nxi) % nyi + 1, rk = r / (nxi * nyi) + 1;
+        int64_t q = rowptr[r];
+        for (int t = 0; t < 7; ++t) {  // the expected entries, in ascending column order
+            const int64_t i = ri + off[t][0], j = rj + off[t][1], k = rk + off[t][2];
+            if (i < 1 || i > nxi || j < 1 || j > nyi || k < 1 || k > nzi) continue;
+            const int64_t cexp = ((k - 1) * nyi + (j - 1)) * nxi + (i - 1);
+            if (q >= rowptr[r + 1] || col[q] != cexp)
+                return "row " + std::to_string(r) + " is not the truncated axis-neighbour pattern";
+            const double v = val[q];
+            if (t == 3) {
+                if (!(v > 0.0) || !std::isfinite(v)) return "row " + std::to_string(r) + " has no positive finite diagonal";
+            } else {
+                uint64_t b;
+                memcpy(&b, &v, sizeof(b));
+                if (!std::isfinite(v) || (have[t] && b != bits[t]))
+                    return "row " + std::to_string(r) + ": the couplings of one offset are not one finite number";
+                bits[t] = b;
+                have[t] = true;
+            }
+            ++q;
+        }
+        if (q != rowptr[r + 1]) return "row " + std::to_string(r) + " has entries outside the axis-neighbour pattern";
+    }
+    for (int t = 0; t < 7; ++t)
+        if (t != 3 && !have[t]) return "a direction has no coupling";
+    if (bits[0] != bits[6] || bits[1] != bits[5] || bits[2] != bits[4]) return "the stencil is not symmetric";
+    for (int k = 0; k < 27; ++k) stencil[k] = 0.0;
+    for (int t = 0; t < 7; ++t)
+        if (t != 3) memcpy(&stencil[slot[t]], &bits[t], sizeof(double));
+    return "";
 }
 
 // mgmc_create / mgmc_create_csr: csr = the fine operator's matrix (null: the constant-coefficient
@@ -2271,6 +2340,10 @@ static int create_impl(const mgmc_config* cfg, const CsrHost* csr, int device, u
         memcpy(specs[l].st, fields.back().centre, sizeof(specs[l].st));
     }
     if (!mats.empty()) h->coarse_csr = mats.back();
+    // the fine matrix is a constant symmetric axis-neighbour stencil plus a diagonal field (mgmc_vardiag_of_csr)
+    double vd_st[27];
+    const bool fine_vardiag = csr && vardiag_of_csr(*cfg, csr->nrow, csr->rowptr.data(), csr->col.data(),
+                                                    csr->val.data(), vd_st).empty();
     const int tail0 = tail_start_by_size(specs, *cfg, h->paths, h->field_mode);  // levels k_tail can take (no quads there)
     size_t lds_limit = 150 * 1024;
     for (size_t l = 0; l < specs.size(); ++l) {
@@ -2324,9 +2397,22 @@ static int create_impl(const mgmc_config* cfg, const CsrHost* csr, int device, u
         const double* st = lv.spec.st;
         const bool has_coarser = l + 1 < specs.size();
         const LevelShape sh{cfg->dim, lv.spec.npoints, lv.L.nx, lv.L.ny, lv.L.nz, lv.field,
-                            st[4] == st[22] && st[10] == st[16] && st[12] == st[14], lv.fold, has_coarser};
+                            st[4] == st[22] && st[10] == st[16] && st[12] == st[14], lv.fold, has_coarser,
+                            l == 0 && fine_vardiag};
         lv.sweep = plan_sweep(sh, h->paths, (int)l, tail0);
         if (has_coarser) lv.res = plan_residual(sh, h->paths, specs[l + 1].n[0], specs[l + 1].n[1], specs[l + 1].n[2]);
+        if (lv.vardiag()) {  // the VD kernels' per-vertex streams, from the coefficient field (which stays)
+            for (double*& p : lv.vd)
+                if (hipMalloc(&p, bytes) != hipSuccess) {
+                    h->levels.push_back(lv);
+                    h->last_error = "device allocation failed (diagonal field)";
+                    return bail(MGMC_E_NOMEM);
+                }
+            for (double* p : lv.vd) hipMemsetAsync(p, 0, bytes, h->stream);
+            const dim3 block(64, 4, 1);
+            hipLaunchKernelGGL(k_vardiag_fill<3>, grid3(lv.L.nx - 1, lv.L.ny - 1, lv.L.nz - 1, block), block, 0, h->stream,
+                               lv.L, lv.F, lv.vd[0], lv.vd[1], lv.vd[2]);
+        }
         if (lv.pingpong()) {
             if (hipMalloc(&lv.x2, cbytes) != hipSuccess) {
                 h->levels.push_back(lv);
@@ -2515,6 +2601,16 @@ int mgmc_stencil_of_csr(const mgmc_config* cfg, int64_t nrow, const int64_t* row
     return MGMC_OK;
 }
 
+int mgmc_vardiag_of_csr(const mgmc_config* cfg, int64_t nrow, const int64_t* rowptr, const int32_t* col,
+                        const double* val, double* stencil) {
+    if (!cfg || !rowptr || !col || !val || !stencil || nrow < 1) return fail(nullptr, MGMC_E_INVALID, "null argument");
+    const std::string e0 = check_csr_shape(*cfg, nrow, rowptr);
+    if (!e0.empty()) return fail(nullptr, MGMC_E_INVALID, "mgmc_vardiag_of_csr: " + e0);
+    const std::string e = vardiag_of_csr(*cfg, nrow, rowptr, col, val, stencil);
+    if (!e.empty()) return fail(nullptr, MGMC_E_UNSUPPORTED, "mgmc_vardiag_of_csr: " + e);
+    return MGMC_OK;
+}
+
 int mgmc_create_stencil_batch(const mgmc_config* cfg, const double* fine_stencil, int device, uint64_t seed,
                               uint64_t chain0, int nchains, mgmc_handle** out) {
     if (!cfg || !fine_stencil || !out) return fail(nullptr, MGMC_E_INVALID, "null argument");
@@ -2565,6 +2661,8 @@ int mgmc_destroy(mgmc_handle* h) {
         if (lv.f) hipFree(lv.f);
         if (lv.F.coef && lv.field) hipFree((void*)lv.F.coef);
         if (lv.rbuf) hipFree(lv.rbuf);
+        for (auto p : lv.vd)
+            if (p) hipFree(p);
         for (auto p : lv.scratch)
             if (p) hipFree(p);
     }
@@ -2622,6 +2720,10 @@ int mgmc_level_kernels(const mgmc_handle* h, int level, char* out, size_t n) {
         switch (lv.sweep) {
             case SweepKernel::FIELD: sweep = "k_fsweep<" + d + ">"; break;
             case SweepKernel::ZSWEEP:
+                if (lv.vardiag()) {  // the VD instance, plain sweeps only (launch_zsweep)
+                    sweep = "k_zsweep_rb7<32," + std::to_string(ZS_TYP) + ",...,0,VD>";
+                    break;
+                }
                 sweep = "k_zsweep_rb7<32," + std::to_string(zsweep_plain_rows(lv, h->nchains)) + ",...,0>";
                 if (!(h->paths & PATH_NO_FUSE_PROLONG))
                     post = "k_zsweep_rb7<32," + std::to_string(tune::ZS_TYP) + ",...,PROLONG>";
@@ -2648,7 +2750,9 @@ int mgmc_level_kernels(const mgmc_handle* h, int level, char* out, size_t n) {
     std::string text = "sweep=" + sweep;
     if (!post.empty()) text += ";post_sweep=" + post;
     // the z-chunk depths the z-sweep launches use (zsweep_depth): plain / fused-prolongation
-    if (sweep.rfind("k_zsweep_rb7", 0) == 0)
+    if (sweep.rfind("k_zsweep_rb7", 0) == 0 && lv.vardiag())
+        text += ";tz=" + std::to_string(zsweep_depth(lv, ZS_TYP, ZS_TZ));
+    else if (sweep.rfind("k_zsweep_rb7", 0) == 0)
         text += ";tz=" + std::to_string(zsweep_depth(lv, ZS_TY, ZS_TZ)) + "/" +
                 std::to_string(zsweep_depth(lv, ZS_TYP, ZS_TZP));
     // sweeps of this level read Box-Muller pairs drawn by an earlier launch (plan_drawn_noise): the
@@ -2671,6 +2775,8 @@ int mgmc_level_kernels(const mgmc_handle* h, int level, char* out, size_t n) {
             text += ";rhs=zero";
             break;
         }
+    // a variable-diagonal level: the z-marching kernels above are the VD instances (a per-vertex diagonal)
+    if (lv.vardiag()) text += ";diag=field";
     if (lv.lr.m > 0)
         text += std::string(";lowrank=") + (lv.lr.rhs_inplace ? "dense,rhs_inplace" : lv.lr.dense_path ? "dense"
                                              : lv.lr.small ? "small" : "rows");

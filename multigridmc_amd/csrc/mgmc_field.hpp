@@ -79,6 +79,25 @@ __global__ void __launch_bounds__(256) k_fsweep(Layout L, double* __restrict__ x
     x[p] = fma(F.omega / d, c - s, x[p]);
 }
 
+// The per-vertex streams of a variable-diagonal level's z-marching kernels (mgmc_zsweep.hpp / mgmc_zrestrict.hpp
+// VD), filled once at create: the centre coefficient, omega / a_cc and the noise scale of every interior vertex,
+// by the expressions of k_fsweep above, so the values are the bits k_fsweep computes per update.  The vectors
+// are zeroed before: boundary and padding stay +0.0.
+template <int DIM>
+__global__ void __launch_bounds__(256) k_vardiag_fill(Layout L, FieldArg F, double* __restrict__ dg,
+                                                      double* __restrict__ wd, double* __restrict__ sdv) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x + 1;
+    const int j = blockIdx.y * blockDim.y + threadIdx.y + 1;
+    const int k = DIM == 3 ? (int)blockIdx.z + 1 : 0;
+    if (i > L.nx - 1 || j > L.ny - 1) return;
+    const long long p = L.at(i, j, k);
+    const double* a = F.coef + field_row<DIM>(F, i, j, k) * F.np;
+    const double d = a[F.diag];
+    dg[p] = d;
+    wd[p] = F.omega / d;
+    sdv[p] = sqrt_rad(d * (2. - F.omega) / F.omega);
+}
+
 // r = f - A x (ZERO_F: r = -A x, i.e. y = A x with the sign folded in by the caller)
 template <int DIM>
 __global__ void __launch_bounds__(256) k_fresidual(Layout L, const double* __restrict__ x,

@@ -185,6 +185,11 @@ struct Level {
     bool fold = false;     // ... and its residuals take the class-folded sum (fold27; MGMC_DISABLE=fold: CSR order)
     FieldArg F;            // ... their device field, pattern and colouring
     double* rbuf = nullptr;  // ... residual scratch (padded layout, zero boundary)
+    // a variable-diagonal level (mgmc_level_plan.hpp vardiag_eligible): a field level the plan gave the z-sweep;
+    // its sweeps are the VD instance (the residual + restriction's: res.vardiag)
+    bool vardiag() const { return field && sweep == SweepKernel::ZSWEEP; }
+    double* vd[3] = {nullptr, nullptr, nullptr};  // ... its a_cc, omega / a_cc and noise-scale vectors (padded layout,
+                                                  // shared by the chains; k_vardiag_fill)
     bool pingpong() const { return sweep_pingpong(sweep); }  // out-of-place sweeps: x <-> x2
     double* buf(int i) const { return i == 0 ? x : x2; }
     LowRankDev lr;

@@ -101,7 +101,19 @@ struct LevelShape {
                        // symmetric 7-point FD stencil to 4 coefficients)
     bool fold;         // reflection-symmetric 27-point stencil whose residuals take the class-folded sum (Level::fold)
     bool has_coarser;  // not the coarsest level
+    bool vardiag = false;  // a field level whose matrix is a constant symmetric axis-neighbour stencil plus a diagonal
+                           // field (mgmc_vardiag_of_csr; st = the six couplings): the shifted-Laplace FD operator
+                           // with any correlation-length model
 };
+
+// A variable-diagonal fine level runs the z-marching kernels' VD instances (mgmc_zsweep.hpp, mgmc_zrestrict.hpp):
+// the constant 7-point stencil with the centre coefficient, omega / a_cc and the noise scale streamed per vertex.
+// The z-sweep's conditions (below) on a field level; MGMC_DISABLE=zsweep leaves the level to the field
+// kernels.
+inline bool vardiag_eligible(const LevelShape& sh, uint32_t paths) {
+    return sh.field && sh.vardiag && sh.dim == 3 && sh.npoints == 7 && sh.fd_symmetric && sh.has_coarser &&
+           (sh.nx % (2 * ZS_XP)) == 0 && !(paths & PATH_NO_ZSWEEP);
+}
 
 // ---- the level's noisy Gibbs sweep ----
 enum class SweepKernel {
@@ -191,6 +203,7 @@ inline JSweepPlan jsweep_plan_dims(int ny, int nz, bool forward, int half, int n
 // level: the level's index; tail_start: the first level k_tail can take by size (tail_start_by_size; -1 none):
 // the levels from there on keep in-place sweeps (no quads, no j-marching), so the tail can run them
 inline SweepKernel plan_sweep(const LevelShape& sh, uint32_t paths, int level, int tail_start) {
+    if (vardiag_eligible(sh, paths)) return SweepKernel::ZSWEEP;  // (its VD instance: Level::vardiag)
     if (sh.field) return SweepKernel::FIELD;
     // fused z-marching sweep: fine 3D 7-point levels whose row splits into 64-pair tiles
     if (sh.dim == 3 && sh.npoints == 7 && sh.fd_symmetric && sh.has_coarser && (sh.nx % (2 * ZS_XP)) == 0 &&
@@ -222,6 +235,7 @@ struct ResidualPlan {
     bool fz = false;          // has an FZ instance: a known-zero right-hand side is not loaded (7-point, not small)
     bool pre_noise = false;   // can draw the coarse level's first pre-sweep's Box-Muller pairs (27-point, not small)
     bool tail_noise = false;  // the small kernel, whose spare workgroups can draw a tail's noise
+    bool vardiag = false;     // the VD instance: the centre coefficient from the level's diagonal vector (7-point, not small)
 };
 
 static_assert(mgmc::tune::ZR_SMALL_NX >= 8, "coarse levels below 8 cells per row take the gather kernel");
@@ -232,6 +246,16 @@ inline ResidualPlan plan_residual(const LevelShape& sh, uint32_t paths, int cnx,
     if (!sh.has_coarser) return p;
     p.npoints = sh.npoints;
     p.sym = sh.fold;
+    if (vardiag_eligible(sh, paths) && !(paths & PATH_NO_ZRESTRICT)) {
+        // the 7-point tile rule below; never the one-wavefront instance (64-wide tiles take any level) and no
+        // LRF / FZ instances
+        p.kind = ResidualKind::ZMARCH;
+        p.vardiag = true;
+        p.cx = 64, p.cy = 4, p.nt = 256;
+        const long long wide_tiles = (long long)((cnx + 62) / 64) * ((cny + 6) / 8) * (cnz - 1);
+        if (wide_tiles >= mgmc::tune::ZR7_WIDE_MIN_TILES) p.cy = 8, p.nt = 512;
+        return p;
+    }
     if (sh.field) {
         p.kind = ResidualKind::FIELD;
         return p;

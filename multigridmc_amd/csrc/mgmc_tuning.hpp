@@ -26,6 +26,9 @@ constexpr int ZS_TZ = 32;
 constexpr int ZS_TYP = 16;
 constexpr int ZS_MINWP = 6;
 constexpr int ZS_TZP = 128;
+// ... the variable-diagonal instance (VD: a matrix level that is the stencil plus a diagonal field) has no values
+// of its own: its three more pair streams need about 30 VGPRs above the plain instance's 80, so it takes the
+// register-bound tile ZS_TYP with no cap on the registers, and the plain sweep's chunks ZS_TZ
 
 // quad passes (k_sweep_quads) on 3D Galerkin levels with rows of at most QUADS_MAXPAIR pairs;
 // workgroup threads: 2D levels, 3D rows of more than 32 pairs, 3D rows of at most 32 pairs

@@ -51,6 +51,9 @@ struct ZRestrictArgs {
     // pn.dst (non-null): every workgroup also draws its share of the Box-Muller pairs of the coarse level's
     // first pre-sweep (pair q -> pn.dst[q], chain 0's key: one chain), after its own march
     PostNoiseJob pn;
+    // VD: the fine level's per-vertex centre coefficient (padded layout, zero on the boundary and in the padding;
+    // one copy for every chain)
+    const double* dg;
 };
 
 // One plane's 3 x 4 window of a residual pair item (rows dy = -1, 0, 1 at byte offsets 0, RB, 2 RB from
@@ -78,10 +81,15 @@ __device__ __forceinline__ void zr_plane12(uint32_t base, double (&v)[12]) {
 // LRF: a low-rank level whose right-hand side is read in place (a.lr: f + e, lr_rhs_pair)
 // FZ: the right-hand side is identically +0.0 (prior sampling, mgmc_capi.hip mark_rhs_zero): f is not
 // loaded, r = 0.0 - A x with the literal (not -A x: the sign of an exact zero); not with LRF
-template <int NPTS, int CX, int CY, int NT, bool ZN = false, bool SYM = false, bool LRF = false, bool FZ = false>
+// VD: a variable-diagonal 7-point level (mgmc_level_plan.hpp vardiag_eligible): the centre coefficient of a
+// residual item is its pair of a.dg, loaded with its f pair; the other six are the level's constants.  The sum
+// is k_fresidual's, term by term.  Not with ZN, LRF, FZ.
+template <int NPTS, int CX, int CY, int NT, bool ZN = false, bool SYM = false, bool LRF = false, bool FZ = false,
+          bool VD = false>
 __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NPTS == 27 && SYM && CX >= 48 ? tune::ZR27_MINW : 1)))
 k_zresrestrict(ZRestrictArgs a) {
     static_assert(!(LRF && FZ), "a patched right-hand side is not zero");
+    static_assert(!VD || (NPTS == 7 && !ZN && !SYM && !LRF && !FZ), "the variable-diagonal instance is the plain 7-point one");
     if (ZN && (int)blockIdx.x >= a.nblk_main) {  // the tail's noise (see ZRestrictArgs)
         const int ch = batch_chain();
         RngKey key = a.key;
@@ -219,6 +227,7 @@ k_zresrestrict(ZRestrictArgs a) {
     }
 
     double2 px[NLX], pf[NLR];
+    double2 pd[VD ? NLR : 1];  // VD: the items' centre coefficients on f's plane
     // the chunk stages x planes 2 K0 - 2 .. 2 K1 and f planes 2 K0 - 1 .. 2 K1 - 1: the last step's loads one
     // plane ahead reload those (never used) instead of fetching the next chunk's planes
     const int kx_last = 2 * K1, kf_last = 2 * K1 - 1;
@@ -241,6 +250,11 @@ k_zresrestrict(ZRestrictArgs a) {
         const double* base = plane_ptr(a.f, k > kf_last ? kf_last : k);
 #pragma unroll
         for (int u = 0; u < NLR; ++u) pf[u] = *reinterpret_cast<const double2*>(base + roff[u]);
+        if constexpr (VD) {
+            const double* dbase = plane_ptr(a.dg, k > kf_last ? kf_last : k);
+#pragma unroll
+            for (int u = 0; u < NLR; ++u) pd[u] = *reinterpret_cast<const double2*>(dbase + roff[u]);
+        }
     };
     // residual of fine plane k over the residual region (vertices outside the fine interior -> 0).
     // The two vertices of a pair advance together through the stencil terms, so their dependent
@@ -261,8 +275,8 @@ k_zresrestrict(ZRestrictArgs a) {
                 y1 += a.S.a[10] * pl[1][o1 - XS];
                 y0 += a.S.a[12] * pl[1][m0];
                 y1 += a.S.a[12] * pl[1][m1];
-                y0 += a.S.a[13] * pl[1][o0];
-                y1 += a.S.a[13] * pl[1][o1];
+                y0 += (VD ? pd[VD ? u : 0].x : a.S.a[13]) * pl[1][o0];
+                y1 += (VD ? pd[VD ? u : 0].y : a.S.a[13]) * pl[1][o1];
                 y0 += a.S.a[14] * pl[1][m0 + 1];
                 y1 += a.S.a[14] * pl[1][m1 + 1];
                 y0 += a.S.a[16] * pl[1][o0 + XS];

@@ -54,6 +54,16 @@ struct ZSweepArgs {
     int zpairs;                // plain sweep: z-chunks in pairs marching towards each other (below)
     long long cs, csc;         // batched chains: doubles between chains of the level / coarse level
     LRRhsArg lr;               // LRF: the right-hand side is f patched in place (mgmc_kernels.hpp)
+    // VD: per-vertex centre coefficient a_cc, omega / a_cc and noise scale sqrt(a_cc (2 - omega) / omega), in the
+    // level's padded layout (zero on the boundary and in the padding), one copy for every chain
+    const double* dg;
+    const double* wdv;
+    const double* sdv;
+};
+
+// the three VD streams of a pair item on one plane
+struct ZVarDiag {
+    double2 d, w, s;
 };
 
 // One pair item of a tile: LDS offset, plane-independent global offset, Philox pair base,
@@ -74,6 +84,12 @@ struct ZItem {
 // load of f is issued and no register holds it; the updates are the same instructions with the literal
 // +0.0 in its place (fma(sd, z, 0.0), not sd * z: the two differ in the sign of an exact zero), so the
 // bits are those of the general instance reading zeros.  Not with LRF.
+// VD: a variable-diagonal level (a matrix level that is this constant stencil plus a diagonal field,
+// mgmc_level_plan.hpp vardiag_eligible): the centre coefficient, omega / a_cc and the noise scale are per-item pairs
+// (ZSweepArgs::dg, wdv, sdv) loaded like f -- a pair at the item's offset on the clamped plane, one step ahead, by
+// core and halo-ring items alike -- and everything else is the constant instance: the same order of terms, Philox
+// ids, Box-Muller and stores.  The values are the ones k_fsweep computes per update (k_vardiag_fill,
+// mgmc_field.hpp), so the sweep is bitwise the two field colour passes.  Plain sweep only: not with PROLONG, LRF, FZ.
 struct RunE0 {
     int value;
 };
@@ -85,10 +101,11 @@ struct BranchE0 {
 constexpr int zs_threads(int TY) { return 256 * ((TY / 2 + 2 + 3) / 4); }
 
 // XP must be 32 (a wave = two rows of 32 pairs); TY a multiple of 4, <= 32
-template <int XP, int TY, int NT, int PROLONG, int MINW, bool LRF = false, bool FZ = false>
+template <int XP, int TY, int NT, int PROLONG, int MINW, bool LRF = false, bool FZ = false, bool VD = false>
 __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MINW))) k_zsweep_rb7(ZSweepArgs a) {
     static_assert(XP == 32 && TY % 4 == 0 && TY <= 32 && NT == zs_threads(TY), "tile shape");
     static_assert(!(LRF && FZ), "a patched right-hand side is not zero");
+    static_assert(!(VD && (PROLONG != 0 || LRF || FZ)), "the variable-diagonal instance is the plain sweep");
     // pairs per LDS row: positions [2*q0-1, 2*q0+2*XP+2] -- the core pairs and one halo pair per side.
     // The halo ring's column items need only their element next to the tile (the even one on the left,
     // the odd one on the right), whose x neighbours are staged; their other element's update reads a
@@ -361,14 +378,25 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MINW)))
             plane_base(a.f, k > k1 ? k1 : (k < k0 - 1 ? k0 - 1 : k)) + foff);
     };
 
+    // VD: the item's diagonal, omega / diagonal and noise-scale pairs on plane k (the planes f is loaded from)
+    auto load_vd = [&](int k) {
+        const int kc = k > k1 ? k1 : (k < k0 - 1 ? k0 - 1 : k);
+        ZVarDiag v;
+        v.d = *reinterpret_cast<const double2*>(plane_base(a.dg, kc) + foff);
+        v.w = *reinterpret_cast<const double2*>(plane_base(a.wdv, kc) + foff);
+        v.s = *reinterpret_cast<const double2*>(plane_base(a.sdv, kc) + foff);
+        return v;
+    };
+
     // fma-chain stencil sum (ascending column order) at LDS offset o of plane k.  The fine FD
     // stencil is symmetric (launch_zsweep checks a[4]=a[22], a[10]=a[16], a[12]=a[14]), so four
     // coefficients serve the seven terms -- same values, same order, same bits.
-    const double cz = a.S.a[4], cy = a.S.a[10], cx = a.S.a[12], cc = a.S.a[13];
+    const double cz = a.S.a[4], cy = a.S.a[10], cx = a.S.a[12], ccl = a.S.a[13];
     // o = LDS offset of the vertex, e = 0 (odd position) / 1 (even position): the x neighbours are
     // the even elements of pairs c-1, c (e = 0) or the odd elements of pairs c, c+1 (e = 1)
     // below = the value at (i, j, k-1): from LDS for the first colour, from a register for the second
-    auto row_sum = [&](int k, int o, int e, double below) {
+    // (cc: the centre coefficient -- the level's constant, or with VD the vertex's)
+    auto row_sum = [&](int k, int o, int e, double below, double cc) {
         const double* s0 = xs + slot(k) * PS;
         const double* sp = xs + slot(k + 1) * PS;
         const int xm = e ? o - WP : o + WP - 1;
@@ -382,7 +410,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MINW)))
         return res;
     };
     // the same sum with the value above (i, j, k+1) from a register (second colour of a downward march)
-    auto row_sum_ba = [&](int k, int o, int e, double below, double above) {
+    auto row_sum_ba = [&](int k, int o, int e, double below, double above, double cc) {
         const double* s0 = xs + slot(k) * PS;
         const int xm = e ? o - WP : o + WP - 1;
         double res = cz * below;
@@ -433,9 +461,16 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MINW)))
         const int E0c_v = E0c.value;
         constexpr bool DN = decltype(DNc)::value;
         constexpr int dz = DN ? -1 : 1;
+        // VD: the item's three pairs travel with f, in the register sets vds[0] (with fA) and vds[1] (with fB); the
+        // second colour's centre coefficient and omega / diagonal of plane p are kept with its right-hand side
+        // (cks[]: x a_cc, y omega / a_cc; [0] with pkA, [1] with pkB), those of plane p-1 come from the other entry.
+        // The constant instances keep their statements apart (if constexpr), so their code is what it was.
+        ZVarDiag vds[2];
+        double2 cks[2];
         auto step = [&](int p, auto ODDc, double2& fcur, double2& fnxt, double pk_in, double& pk_out)
                         __attribute__((always_inline)) {
             constexpr bool odd_step = decltype(ODDc)::value;
+            constexpr int vc = odd_step ? 1 : 0;  // (VD) this step's register set; the other takes the next plane's
             const int e_step = odd_step ? 1 - E0c_v : E0c_v;  // first-colour element on plane p
             // the two colour sections below take the element as ec.value: a constant (this copy of the march
             // is compiled for E0), a run-time value (RunE0: selects), or (BranchE0) a constant again, under a
@@ -465,6 +500,9 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MINW)))
                 if constexpr (!FZ) {
                     if (active_wave) fnxt = load_f(p + dz);
                 }
+                if constexpr (VD) {
+                    if (active_wave) vds[1 - vc] = load_vd(p + dz);
+                }
             }
             __syncthreads();
             // first colour on plane p: c = fma(sd, z, f), x = fma(omega/diag, c - S, x); the second
@@ -477,13 +515,26 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MINW)))
                     const int e = ec.value;
                     const int o1 = t.lds + e * WP;
                     const bool inf = e ? in1 : in0;  // (compile-time choice)
-                    if (inf) {
-                        const double res = row_sum(p, o1, e, xs[slot(p - 1) * PS + o1]);
-                        const double crhs = fma(sd, e ? z.y : z.x, e ? fv.y : fv.x);
-                        double* s0 = xs + slot(p) * PS;
-                        s0[o1] = fma(wd, crhs - res, s0[o1]);
+                    if constexpr (VD) {
+                        // this element's members of the item's pairs; the other element's go to the second colour
+                        const ZVarDiag& v = vds[vc];
+                        if (inf) {
+                            const double res = row_sum(p, o1, e, xs[slot(p - 1) * PS + o1], e ? v.d.y : v.d.x);
+                            const double crhs = fma(e ? v.s.y : v.s.x, e ? z.y : z.x, e ? fv.y : fv.x);
+                            double* s0 = xs + slot(p) * PS;
+                            s0[o1] = fma(e ? v.w.y : v.w.x, crhs - res, s0[o1]);
+                        }
+                        pk_out = fma(e ? v.s.x : v.s.y, e ? z.x : z.y, e ? fv.x : fv.y);
+                        cks[vc] = e ? make_double2(v.d.x, v.w.x) : make_double2(v.d.y, v.w.y);
+                    } else {
+                        if (inf) {
+                            const double res = row_sum(p, o1, e, xs[slot(p - 1) * PS + o1], ccl);
+                            const double crhs = fma(sd, e ? z.y : z.x, e ? fv.y : fv.x);
+                            double* s0 = xs + slot(p) * PS;
+                            s0[o1] = fma(wd, crhs - res, s0[o1]);
+                        }
+                        pk_out = fma(sd, e ? z.x : z.y, e ? fv.x : fv.y);
                     }
-                    pk_out = fma(sd, e ? z.x : z.y, e ? fv.x : fv.y);
                 });
             }
             if constexpr (PF2 && !FZ) fcur = load_f(p + 2);  // this step's f is used up: the registers take f(p+2)
@@ -503,9 +554,11 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MINW)))
                         if (inf) {
                             // DN: below = plane p (this step's first colour, LDS), above = plane p+2 (fb); the
                             // slot of p+2 takes the next step's deposit, so it is not read here
-                            const double res =
-                                DN ? row_sum_ba(k, o1, e, xs[slot(p) * PS + o1], fb) : row_sum(k, o1, e, fb);
-                            sv = fma(wd, pk_in - res, sv);
+                            double cc2 = ccl, wd2 = wd;
+                            if constexpr (VD) cc2 = cks[1 - vc].x, wd2 = cks[1 - vc].y;
+                            const double res = DN ? row_sum_ba(k, o1, e, xs[slot(p) * PS + o1], fb, cc2)
+                                                  : row_sum(k, o1, e, fb, cc2);
+                            sv = fma(wd2, pk_in - res, sv);
                         }
                         double* dst = a.xout + (long long)k * L.sp + t.goff;
                         // (x, y) = (odd, even) element; the second colour is element e here
@@ -530,6 +583,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MINW)))
             fB = load_f(k0);
         } else if (active_wave) {
             fA = load_f(pst);
+            if constexpr (VD) vds[0] = load_vd(pst);
         }
         if (active_wave && interior_plane(pst)) z = noise(pst);
         if constexpr (DN) {

@@ -269,6 +269,21 @@ class SparseMatrixOperator(ShiftedLaplaceFDOperator):
         check(rc)
         return st
 
+    def vardiag_stencil(self, config):
+        """The constant symmetric axis-neighbour stencil (27 values, centre 0.0) of a 3D matrix that is such a
+        stencil plus a positive diagonal field (mgmc_vardiag_of_csr), or None.  mgmc_create_csr runs the same
+        check: the fine level of such a matrix takes the z-marching kernels with a per-vertex diagonal."""
+        lib = load_library()
+        rowptr, col, val = self._csr
+        st = np.zeros(27)
+        rc = lib.mgmc_vardiag_of_csr(ctypes.byref(config), len(rowptr) - 1,
+                                     rowptr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                     col.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _dp(val), _dp(st))
+        if rc == _native.MGMC_E_UNSUPPORTED:
+            return None
+        check(rc)
+        return st
+
 
 def sampler_csr_matrix(rowptr, col, val, n: int):
     """(rowptr, col, val) as a scipy CSR matrix of shape (n, n)."""
@@ -655,7 +670,10 @@ class MultigridMCSampler:
         bytes; the key is absent otherwise; "quads": "window" on a 3D "k_sweep_quads<3>" level whose row
         length -- nx/2 pairs, not a divisor of 64 -- selects the three-load window instances instead of the
         lane-shift ones; "tz": "<plain>/<post>" on a level swept by k_zsweep_rb7: the z-chunk depths, in planes,
-        of the plain and of the fused-prolongation sweep launches)"""
+        of the plain and of the fused-prolongation sweep launches; "diag": "field" on level 0 of a matrix handle
+        whose fine matrix is a constant stencil plus a diagonal field (vardiag_stencil): the level runs the
+        z-marching kernels' variable-diagonal instances, "tz" is then the one depth of its plain sweeps, and it has
+        no "post_sweep" and never "rhs")"""
         buf = ctypes.create_string_buffer(512)
         self._chk(self.lib.mgmc_level_kernels(self.handle, int(level), buf, 512))
         return dict(kv.split("=", 1) for kv in buf.value.decode().split(";"))
