@@ -18,7 +18,12 @@ section 4, philox_normal.h, the header of mgmc_lowrank.hpp).
   C  a whole cycle x' = S x + G f + W xi leaves N(Q^-1 f, Q^-1) invariant: S + G Q = I and
      W W^T = Q^-1 - S Q^-1 S^T, W fitted against every normal the counter contract lets the cycle draw;
   D  a cycle is the composition of these pieces: the reference's recursion (multigridmc_sampler.cc:103-138)
-     restated over the component entry points reproduces apply() bit for bit.
+     restated over the component entry points reproduces apply() bit for bit;
+  R  the residual + restriction is P^T (b - A_l x) componentwise (LevelAlgebra.residual_ratio, bound derived:
+     residual_bound);
+  G  the level matrices themselves are the Galerkin products P^T A_(l-1) P (galerkin_defects).
+Matrix-built problems (Problem kind "matrix": what the library takes through mgmc_create_csr) get all of them; the
+colours of their reach-2 levels are the coordinates mod 3.
 
 Tolerance of A and B (componentwise, |lhs - rhs| <= C_TOL * EPS * s): s is the same expression with absolute
 values, every low-rank dot product weighted with the number of entries of its column (the gamma factor of a sum of
@@ -43,17 +48,40 @@ KAPPA_SQ = 25.0
 # ------------------------------------------------------------------------------------------------
 # problems: one operator, and the three things built from it (device sampler, replay oracle, FAITHFUL oracle)
 # ------------------------------------------------------------------------------------------------
+PERIODIC = mg.PeriodicCorrelationLengthModel(0.2, 0.4)
+CONSTANT = mg.ConstantCorrelationLengthModel(0.2)  # kappa^2 = 25
+MATRIX_OPERATORS = {"fd": (mg.ShiftedLaplaceFDOperator, 0), "fem": (mg.ShiftedLaplaceFEMOperator, 1),
+                    "squared": (mg.SquaredShiftedLaplaceFDOperator, 2)}  # (class, the oracle's pde code)
+
+
 class Problem:
     """kind "fd" | "fem" | "stencil" (stencil: a tests/user_stencils.py name) on `shape` cells; kw over the SOR /
-    SSOR-coarse defaults; meas = (radius, number of measurements, measure_global) as in tests/test_gpu_lowrank.py."""
+    SSOR-coarse defaults; meas = (radius, number of measurements, measure_global) as in tests/test_gpu_lowrank.py.
 
-    def __init__(self, kind, shape, kw, meas=None, stencil=None, kappa_sq=KAPPA_SQ):
+    kind "matrix": an operator the library takes as a matrix (mgmc_create_csr).  pde "fd" | "fem" | "squared" with
+    model "periodic" (PERIODIC) or "constant" (CONSTANT), or pde "dominant": the hand-made anisotropic matrix
+    tests.test_vardiag_host.dominant_matrix (cx != cy != cz, random dominant diagonal).  The sampler gets the
+    library's operator; the oracles get the oracle's own assembly of the same operator (O.operator_csr), so that
+    matrix(0)'s assertion compares two assemblies."""
+
+    def __init__(self, kind, shape, kw, meas=None, stencil=None, kappa_sq=KAPPA_SQ, pde=None, model="periodic"):
         self.kind, self.shape, self.meas, self.stencil, self.kappa_sq = kind, tuple(shape), meas, stencil, kappa_sq
+        self.pde, self.model = pde, model
+        assert (kind == "matrix") == (pde is not None) and model in ("periodic", "constant")
         self.params = mg.MultigridParameters(**{"nlevel": 3, "smoother": "SOR", "coarse_solver": "SSOR", **kw})
         self.lat = mg.Lattice(*shape)
         self._faithful = None
 
+    def _dominant(self):
+        from tests.test_vardiag_host import dominant_matrix
+        return dominant_matrix(self.shape)
+
     def operator(self):
+        if self.kind == "matrix":
+            assert self.meas is None
+            if self.pde == "dominant":
+                return mg.SparseMatrixOperator(self.lat, self._dominant())
+            return MATRIX_OPERATORS[self.pde][0](self.lat, PERIODIC if self.model == "periodic" else CONSTANT)
         if self.kind == "fd":
             op = mg.ShiftedLaplaceFDOperator(self.lat, self.kappa_sq)
         elif self.kind == "fem":
@@ -72,6 +100,17 @@ class Problem:
         return self.operator().get_B() if self.meas is not None else None
 
     def oracle(self, mode=O.MULTICOLOUR, seed=0, chain=0):
+        if self.kind == "matrix":
+            if self.pde == "dominant":
+                A = self._dominant()
+                rowptr, col, val = A.indptr, A.indices, A.data
+            else:
+                rowptr, col, val = O.operator_csr(self.shape, MATRIX_OPERATORS[self.pde][1], self.model == "periodic",
+                                                  Lambda=CONSTANT.Lambda, Lambda_min=PERIODIC.Lambda_min,
+                                                  Lambda_max=PERIODIC.Lambda_max)
+            o = O.Oracle.csr(self.shape, self.params, rowptr, col, val, mode=mode, seed=seed)
+            o.reseed(seed, chain)  # (orc_create_csr takes no chain id)
+            return o
         if self.kind == "fd":
             o = O.Oracle.fd_own(self.shape, self.params, self.kappa_sq, mode=mode, seed=seed, chain=chain)
         elif self.kind == "fem":
@@ -142,10 +181,15 @@ def coords(shape):
 
 def colour_of(A, shape, level):
     """The documented colours: (i + j + k) & 1 on a fine level whose couplings are all axis neighbours (5 / 7
-    point), the parity bits (i & 1) | (j & 1) << 1 | (k & 1) << 2 on 9 / 27-point levels."""
+    point), the parity bits (i & 1) | (j & 1) << 1 | (k & 1) << 2 on 9 / 27-point levels; a level with a coupling
+    two vertices apart in a direction (the squared operator and its Galerkin levels) takes the coordinates mod 3,
+    (i % 3) + 3 (j % 3) + 9 (k % 3), ascending forward (the header of mgmc_field.hpp)."""
     xyz = coords(shape)
     C = A.tocoo()
-    off_axis = (np.abs(xyz[:, C.row] - xyz[:, C.col]).sum(axis=0) > 1) & (C.data != 0.0)
+    apart = np.abs(xyz[:, C.row] - xyz[:, C.col])
+    if ((apart.max(axis=0) > 1) & (C.data != 0.0)).any():
+        return sum((xyz[d] % 3) * 3 ** d for d in range(len(shape)))
+    off_axis = (apart.sum(axis=0) > 1) & (C.data != 0.0)
     if level == 0 and not off_axis.any():
         return xyz.sum(axis=0) & 1
     return sum((xyz[d] & 1) << d for d in range(len(shape)))
@@ -296,6 +340,50 @@ class LevelAlgebra:
             got = got + ld + lx - B @ (xip / np.sqrt(sig))
             s = s + ls + abs(B) @ (np.abs(xip) / np.sqrt(sig))
         return float(np.max(np.abs(got / self.sd - xi) / (EPS * s / self.sd)))
+
+
+    # R: the residual + restriction onto the next level
+    def residual_bound(self):
+        """The bound of residual_ratio, derived: the row sum's rounding factor (its number of terms, the largest
+        row's), one for the subtraction from b, and 3^d for the restriction's sum (its weights are powers of two)."""
+        return float(np.diff(self.A.indptr).max() + 1 + 3 ** len(self.shape))
+
+    def residual_ratio(self, be, b, x):
+        """R: residual_restrict(level, b, x) = P^T (b - A_l x) componentwise, P from its definition; the ratio
+        |got - ref| / (EPS P^T (|b| + |A_l| |x|))."""
+        P = interpolation(self.shape)
+        got = be.residual_restrict(self.level, b, x)
+        assert got.shape == (P.shape[1],) and np.all(np.isfinite(got))
+        ref = P.T @ (b - self.A @ x)
+        s = P.T @ (np.abs(b) + self.absA @ np.abs(x))
+        return float(np.max(np.abs(got - ref) / (EPS * s)))
+
+
+def check_residuals(prob, be, rng, algebras):
+    """R on every level that has a coarser one: {level: (ratio, its bound)}; prints the largest ratio."""
+    out = {}
+    for la in algebras[:-1]:
+        b, x = rng.standard_normal(la.n), rng.standard_normal(la.n)
+        out[la.level] = (la.residual_ratio(be, b, x), la.residual_bound())
+    print("algebra R (residual + restriction): " + "  ".join(f"level {l} ratio {r:.2f} (bound {c:.0f})"
+                                                              for l, (r, c) in out.items()))
+    return out
+
+
+GALERKIN_TOL = 64.0  # in EPS max |A_l|: the association of at most 3^d x 3^d terms per entry
+
+
+def galerkin_defects(prob):
+    """G: A_l = P^T A_(l-1) P with P = interpolation(...) on the FAITHFUL oracle's level matrices, which makes them
+    independent of any Galerkin code: [max |A_l - P^T A_(l-1) P| / (EPS max |A_l|)] for l = 1 .. nlevel - 1."""
+    out = []
+    for level in range(1, prob.params.nlevel):
+        P = interpolation(prob.level_shape(level - 1))
+        A = prob.matrix(level)
+        D = abs(sp.csr_matrix(P.T @ prob.matrix(level - 1) @ P) - A)
+        out.append(float((D.max() if D.nnz else 0.0) / (EPS * abs(A).max())))
+    print("algebra G (Galerkin products), per level from 1: " + "  ".join(f"{v:.3g}" for v in out))
+    return out
 
 
 def level_algebras(prob, symmetric=True):

@@ -36,7 +36,10 @@ struct Cycle {
     int cycle = 1, npre = 1, npost = 1;
     bool ssor = false;
 };
-static Hier walk(int dim, int nx, int ny, int nz, int nlevel, bool fem, uint32_t paths, Cycle cy = Cycle()) {
+// matrix: a matrix handle (mgmc_create_csr) whose fine matrix is a constant symmetric 7-point stencil plus a diagonal
+// field: every level a field level, the fine one variable-diagonal, no tail
+static Hier walk(int dim, int nx, int ny, int nz, int nlevel, bool fem, uint32_t paths, Cycle cy = Cycle(),
+                 bool matrix = false) {
     Hier H;
     for (int l = 0; l < nlevel; ++l) {
         const bool galerkin = fem || l > 0;
@@ -46,9 +49,10 @@ static Hier walk(int dim, int nx, int ny, int nz, int nlevel, bool fem, uint32_t
         s.nx = nx >> l;
         s.ny = ny >> l;
         s.nz = dim == 3 ? nz >> l : 0;
-        s.field = false;
+        s.field = matrix;
+        s.vardiag = matrix && l == 0;
         s.fd_symmetric = !fem;
-        s.fold = dim == 3 && !fem && l > 0 && !(paths & PATH_NO_FOLD);
+        s.fold = dim == 3 && !fem && !matrix && l > 0 && !(paths & PATH_NO_FOLD);
         s.has_coarser = l + 1 < nlevel;
         H.sh.push_back(s);
     }
@@ -57,7 +61,7 @@ static Hier walk(int dim, int nx, int ny, int nz, int nlevel, bool fem, uint32_t
         [&](int l, size_t* v, size_t*) {
             const LevelShape& s = H.sh[l];
             *v = tail_level_doubles(s.dim, s.nx, s.ny, s.nz);
-            return s.npoints == (s.dim == 3 ? 27 : 9);
+            return !s.field && s.npoints == (s.dim == 3 ? 27 : 9);
         },
         [&](int ntail) { return tail_run_ops(ntail, cy.cycle, cy.npre, cy.npost, cy.ssor); });
     for (int l = 0; l < nlevel; ++l) {
@@ -95,21 +99,25 @@ static uint32_t flag_of(const char* token) {
 }
 
 // "plan" mode (tests/test_tuning_host.py, compiled against a re-tuned mgmc_tuning.hpp):
-//   level_plan_host plan <nx> <ny> <nz> <nlevel> [MGMC_DISABLE list]     (nz = 0: a 2D lattice; FD prior)
-// prints one line per level,
-//   level <l> sweep <KIND> [lanes|window] [js <chunks per plane>x<steps per chunk>] residual <KIND> [np <n> cx <n> cy <n> nt <n>] [small] [sym] tail <lt>
+//   level_plan_host plan <nx> <ny> <nz> <nlevel> [MGMC_DISABLE list] [vardiag]   (nz = 0: a 2D lattice; FD prior)
+// (vardiag: the matrix handle of the periodic-kappa^2 FD operator instead) prints one line per level,
+//   level <l> sweep <KIND> [rows <z-sweep tile rows of the VD instance>] [lanes|window] [js <chunks per plane>x<steps per chunk>] residual <KIND> [np <n> cx <n> cy <n> nt <n>] [small] [sym] [vd] tail <lt>
 static int print_plan(int argc, char** argv) {
     if (argc < 6) return 2;
     const int nx = atoi(argv[2]), ny = atoi(argv[3]), nz = atoi(argv[4]), nlevel = atoi(argv[5]);
     const uint32_t paths = argc > 6 && argv[6][0] ? flag_of(argv[6]) : 0;
     if (argc > 6 && argv[6][0] && !paths) return 2;
     const int dim = nz > 0 ? 3 : 2;
-    const Hier H = walk(dim, nx, ny, nz, nlevel, false, paths);
+    const bool matrix = argc > 7 && std::string(argv[7]) == "vardiag";
+    if (argc > 7 && !matrix) return 2;
+    const Hier H = walk(dim, nx, ny, nz, nlevel, false, paths, Cycle(), matrix);
     static const char* const sk[] = {"COLOUR", "FIELD", "PAIRS", "QUADS", "JSWEEP", "RB2D", "ZSWEEP"};
     static const char* const rk[] = {"NONE", "FIELD", "GATHER", "ZMARCH"};
     for (int l = 0; l < nlevel; ++l) {
         const ResidualPlan& r = H.res[l];
         std::printf("level %d sweep %s", l, sk[(int)H.sweep[l]]);
+        // (the VD instance of the z-sweep takes the fused-prolongation sweep's tile rows: launch_zsweep)
+        if (H.sweep[l] == SK::ZSWEEP && H.sh[l].vardiag) std::printf(" rows %d", mgmc::tune::ZS_TYP);
         if (H.sweep[l] == SK::QUADS && dim == 3) std::printf(" %s", quads_lanes(dim, H.sh[l].nx / 2) ? "lanes" : "window");
         if (H.sweep[l] == SK::JSWEEP) {  // forward sweep, first half, the 256 compute units of an MI355X
             const JSweepPlan p = jsweep_plan_dims(H.sh[l].ny, H.sh[l].nz, true, 0, 256, jsweep_lds_bytes(H.sh[l].nx / 2),
@@ -120,6 +128,7 @@ static int print_plan(int argc, char** argv) {
         if (r.kind == RK::ZMARCH) std::printf(" np %d cx %d cy %d nt %d", r.npoints, r.cx, r.cy, r.nt);
         if (r.small) std::printf(" small");
         if (r.sym) std::printf(" sym");
+        if (r.vardiag) std::printf(" vd");
         std::printf(" tail %d\n", H.tail);
     }
     return 0;

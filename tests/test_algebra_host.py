@@ -13,11 +13,22 @@ Largest ratios |lhs - rhs| / (EPS s) measured on the oracle (bound C_TOL = 8), p
     fem2d32 2.09 / 3.57 / 2.25            c27_24x20x12 4.17 / 4.45 / 3.54
 (B of 2d32_point_global is 75.7 at the three measured vertices without the Woodbury term of s,
 algebra.LevelAlgebra._lowrank_terms.)  Whole cycles: CYCLE_REFERENCE below.
+Matrix-built problems (Oracle.csr on the oracle's own assembly; the device takes them through mgmc_create_csr):
+    m_fd_periodic_24x20x12_w11 2.09 / 4.32 / 2.59   m_fd_periodic_34x18_w08 1.53 / 3.79 / 2.18
+    m_fem_periodic_16 2.52 / 5.31 / 2.77            m_squared_32 2.39 / 4.32 / 2.61 (9 colours on all 3 levels)
+    m_squared_32_periodic 1.87 / 3.52 / 2.47 (9 colours, not symmetric)   m_dominant_16x12x8 2.33 / 3.48 / 2.32
+  R (residual + restriction against P^T (b - A_l x) in scipy; bound: largest row + 1 + 3^d = 15 .. 55): ratio 0.00
+  on every level of all six; G (A_l against P^T A_(l-1) P, bound 64 EPS max |A_l|): 0.0 on every level of all six.
+Composition: m_fd_periodic_24x20x12_w11 9.68e-16, m_squared_32_ssor_W 1.60e-14; apply() equals the replay bit for
+bit in both.
 
 What the checks catch, shown on mutated copies of the oracle (never committed): the noise scale times 1.01 on
 odd vertices -> B 8.9e13 (bound 8), stationarity 1.7e-2; the sweep tag & ~1 (two sweeps share a tag) ->
 stationarity 0.34; the backward colour order ascending -> A 8.5e15; sqrt(1 / Sigma) replaced by 1 / Sigma in the
-low-rank noise -> B 4.9e13, stationarity 24.
+low-rank noise -> B 4.9e13, stationarity 24.  On m_fd_periodic_24x20x12_w11: the residual's row sum with the
+diagonal of the pair's other vertex -> R 1.7e13 / 3.5e12 on levels 0 / 1 (bounds 35 / 55), composition 1.7e-2
+(bound 1e-12); with one constant diagonal -> R 7.0e12 / 7.4e12, composition 4.1e-3; the noise scale times 1.01 ->
+B 8.9e13 (A, R, G and the composition unchanged).
 """
 import numpy as np
 import pytest
@@ -40,7 +51,17 @@ SWEEP_CASES = {
                              meas=(0.1, 2, True)),
     "fem2d32": dict(kind="fem", shape=(32, 32), kw=dict(nlevel=3, omega=0.9)),
     "c27_24x20x12": dict(kind="stencil", shape=(24, 20, 12), kw=dict(nlevel=3), stencil="C27", symmetric=False),
+    # matrix-built problems (mgmc_create_csr on the device): per-vertex coefficients, the squared operator's reach-2
+    # levels in 9 colours (with periodic kappa^2 its matrix is not symmetric), a hand-made anisotropic matrix
+    "m_fd_periodic_24x20x12_w11": dict(kind="matrix", pde="fd", shape=(24, 20, 12), kw=dict(nlevel=3, omega=1.1)),
+    "m_fd_periodic_34x18_w08": dict(kind="matrix", pde="fd", shape=(34, 18), kw=dict(nlevel=3, omega=0.8)),
+    "m_fem_periodic_16": dict(kind="matrix", pde="fem", shape=(16, 16, 16), kw=dict(nlevel=3)),
+    "m_squared_32": dict(kind="matrix", pde="squared", model="constant", shape=(32, 32), kw=dict(nlevel=3)),
+    "m_squared_32_periodic": dict(kind="matrix", pde="squared", shape=(32, 32), kw=dict(nlevel=3), symmetric=False),
+    "m_dominant_16x12x8": dict(kind="matrix", pde="dominant", shape=(16, 12, 8), kw=dict(nlevel=2)),
 }
+MATRIX_CASES = [name for name, case in SWEEP_CASES.items() if case["kind"] == "matrix"]
+NINE_COLOUR_CASES = ["m_squared_32", "m_squared_32_periodic"]
 
 
 def problem(case):
@@ -91,6 +112,27 @@ def test_sweeps_are_the_sor_splitting_with_unit_noise(name):
     assert worst <= AL.C_TOL, ratios
 
 
+def check_matrix_levels(prob, be, symmetric, nine_colours, algebras=None):
+    """R on every level of a matrix-built problem through `be`, G on its FAITHFUL matrices, and the colour count
+    of the squared operator's levels (shared with tests/test_gpu_algebra.py)."""
+    las = algebras or AL.level_algebras(prob, symmetric)
+    if nine_colours:
+        assert all(len(np.unique(la.colour)) == 9 for la in las), [len(np.unique(la.colour)) for la in las]
+    for level, (ratio, bound) in AL.check_residuals(prob, be, np.random.default_rng(8), las).items():
+        assert ratio <= bound, (level, ratio, bound)
+    defects = AL.galerkin_defects(prob)
+    assert len(defects) == prob.params.nlevel - 1 and max(defects) <= AL.GALERKIN_TOL, defects
+
+
+@pytest.mark.parametrize("name", MATRIX_CASES)
+def test_matrix_levels_restrict_residuals_and_are_galerkin_products(name):
+    """R and G: the residual + restriction against P^T (b - A_l x) in scipy, and A_l = P^T A_(l-1) P."""
+    case = SWEEP_CASES[name]
+    prob = problem(case)
+    check_matrix_levels(prob, prob.oracle(seed=SEED, chain=CHAIN), case.get("symmetric", True),
+                        name in NINE_COLOUR_CASES)
+
+
 # a batch's chain c draws the stream of chain id CHAIN + c.  With coarse_scaling 0 the coarse correction drops out
 # of the cycle exactly, so one cycle with (npresmooth, npostsmooth) = (1, 0) is the forward sweep under tag 0 and
 # with (0, 1) the backward sweep under the first tag after the coarse sampler's: B (and A) through the cycle itself
@@ -136,6 +178,11 @@ CYCLE_CASES = {
     "2d8_ball_global": dict(kind="fd", shape=(8, 8), kw=dict(nlevel=3), meas=(0.2, 4, True)),
     "3d8_2lvl_cs2": dict(kind="fd", shape=(8, 8, 8), kw=dict(nlevel=2, ncoarsesmooth=2)),
     "fem2d8": dict(kind="fem", shape=(8, 8), kw=dict(nlevel=3, npresmooth=2)),
+    "2d8_fd_periodic": dict(kind="matrix", pde="fd", shape=(8, 8), kw=dict(nlevel=3, ncoarsesmooth=2)),
+    "2d8_fem_periodic_ssor_W": dict(kind="matrix", pde="fem", shape=(8, 8),
+                                    kw=dict(nlevel=3, cycle=2, smoother="SSOR", omega=1.1)),
+    "2d8_squared": dict(kind="matrix", pde="squared", model="constant", shape=(8, 8), kw=dict(nlevel=2)),
+    "3d8_fd_periodic": dict(kind="matrix", pde="fd", shape=(8, 8, 8), kw=dict(nlevel=2, ncoarsesmooth=2)),
 }
 # (max |S + G Q - I|, max |W W^T - (Q^-1 - S Q^-1 S^T)| / max |Q^-1|) of the CPU oracle, the reference of both
 # files; the bound is CYCLE_SLACK times it (conditioning of the fit), at least ten orders below the smallest defect
@@ -147,6 +194,10 @@ CYCLE_REFERENCE = {
     "2d8_ball_global": (5.75e-14, 2.00e-15),  # K 781, 488 columns, 6 tags, fit 1.3e-15 (Q carries B Sigma^-1 B^T)
     "3d8_2lvl_cs2": (1.95e-15, 1.52e-15),    # K 5018, 3136 columns, 6 tags, fit 1.4e-15
     "fem2d8": (1.47e-15, 1.68e-15),          # K 896, 560 columns, 8 tags, fit 1.0e-15
+    "2d8_fd_periodic": (1.60e-15, 1.40e-15),          # K 896, 560 columns, 8 tags, fit 1.1e-15
+    "2d8_fem_periodic_ssor_W": (1.25e-15, 1.93e-15),  # K 1613, 1008 columns, 16 tags, fit 1.3e-15
+    "2d8_squared": (8.37e-14, 1.32e-15),              # K 538, 336 columns, 4 tags, fit 1.3e-15 (max |Q| = 1.6e5)
+    "3d8_fd_periodic": (1.79e-15, 1.92e-15),          # K 5018, 3136 columns, 6 tags, fit 1.5e-15
 }
 CYCLE_SLACK = 100.0
 FIT_TOL = 1e-11  # fit residual / max |eta|; also the bound of the rows of W that must vanish (a least-squares
@@ -192,6 +243,9 @@ COMPOSITION_CASES = {
     "2d_34x18_ssor_W": dict(kind="fd", shape=(34, 18), kw=dict(nlevel=3, cycle=2, smoother="SSOR", npresmooth=2,
                                                                omega=0.8)),
     "2d32_point_global": SWEEP_CASES["2d32_point_global"],
+    "m_fd_periodic_24x20x12_w11": SWEEP_CASES["m_fd_periodic_24x20x12_w11"],
+    "m_squared_32_ssor_W": dict(kind="matrix", pde="squared", model="constant", shape=(32, 32),
+                                kw=dict(nlevel=3, cycle=2, smoother="SSOR", npresmooth=2)),
 }
 CONSISTENCY_TOL = 1e-12  # the project's fixed-point tolerance
 

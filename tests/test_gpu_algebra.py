@@ -21,6 +21,20 @@ Whole cycles (consistency / stationarity; reference and bound in test_algebra_ho
     fit residuals 1.0e-15 .. 1.6e-15, rows of W under tags T, T + 1 below 8e-17 of max |eta|
 Composition: T_k(mu, Q mu) - T_k(0, 0) = mu to 2.08e-15 (3d_jsweep_tail), 1.36e-15 (2d_200x120), 8.13e-14
 (3d_96x48x48_points); apply() equals the replay bit for bit in all three, no op needed the componentwise bound.
+
+Matrix handles (mgmc_create_csr: Problem kind "matrix"; the matrices from the oracle's own assembly and scipy
+products, the reach-2 colours from the rule in mgmc_field.hpp), measured on the MI355X, A / B / A and B at once:
+    vd_128x34x18 2.66 / 5.35 / 3.36   vd_192x48x40 4.18 / 5.19 / 3.57   vd_dominant_128x34x18 4.42 / 6.04 / 4.28
+    field2d_fd_periodic_64 1.92 / 3.93 / 2.22   field3d_fem_periodic_16 2.52 / 5.31 / 2.77
+    field2d_squared_32 2.39 / 4.32 / 2.61       field2d_squared_32_periodic 1.87 / 3.52 / 2.47
+  R (residual_restrict against P^T (b - A_l x) in scipy; bound: largest row + 1 + 3^d = 15 .. 55): ratio 0.00 on every
+  level of all seven (k_zresrestrict<7,64,4,...,VD>, k_fresidual + k_restrict: separate multiplies and adds in
+  ascending column order, the order scipy sums in); G: 0.0 on every level.
+  Whole cycles: 2d8_fd_periodic 1.60e-15 / 1.40e-15  2d8_fem_periodic_ssor_W 1.25e-15 / 1.59e-15
+  2d8_squared 8.37e-14 / 1.02e-15  3d8_fd_periodic 1.79e-15 / 1.54e-15 (fit 1.1e-15 .. 1.3e-15, extra rows < 8e-17).
+  Composition: vd_192x48x40_ssor_W 2.97e-15, field2d_squared_32_ssor_W 1.53e-14, bit for bit both.
+The vd_* cases run with every high word of seed, chain, tag and sample index set: the VD sweep's noise is held to
+the full 64-bit counter contract here.
 """
 import numpy as np
 import pytest
@@ -33,6 +47,8 @@ pytestmark = pytest.mark.gpu
 SEED, CHAIN, TAG, SAMPLE = H.SEED, H.CHAIN, H.TAG, H.SAMPLE
 
 ZS = {"sweep^": "k_zsweep_rb7<", "post_sweep^": "k_zsweep_rb7<"}
+VD = {"sweep^": "k_zsweep_rb7<", "sweep$": ",VD>", "residual_restrict^": "k_zresrestrict<7,", "diag": "field"}
+FIELD3 = {"sweep": "k_fsweep<3>", "residual_restrict": "k_fresidual + k_restrict"}
 # name: (problem, labels per level: {key: value}, "key^" a prefix)
 SWEEP_CASES = {
     # k_zsweep_rb7, plain and fused-prolongation instance; partial tiles in y and z
@@ -69,17 +85,37 @@ SWEEP_CASES = {
     "3d32_ball_global": (H.SWEEP_CASES["3d32_ball_global"],
                          {0: {"lowrank": "dense"}, 1: {"sweep": "k_sweep_pairs<3>", "lowrank": "small"},
                           2: {"lowrank": "small"}}),
+    # ---- matrix handles (mgmc_create_csr); these also run R on every level and G (H.check_matrix_levels) ----
+    # the variable-diagonal z-marching instances: periodic kappa^2 and the hand-made anisotropic matrix; with three
+    # levels a field level (k_fsweep, k_fresidual + k_restrict) below them
+    "vd_128x34x18": (dict(kind="matrix", pde="fd", shape=(128, 34, 18), kw=dict(nlevel=2, omega=0.9)), {0: VD}),
+    "vd_192x48x40": (dict(kind="matrix", pde="fd", shape=(192, 48, 40), kw=dict(nlevel=3)), {0: VD, 1: FIELD3}),
+    "vd_dominant_128x34x18": (dict(kind="matrix", pde="dominant", shape=(128, 34, 18), kw=dict(nlevel=2)), {0: VD}),
+    # the field kernels with 2 (red-black), 8 (parities) and 9 (coordinates mod 3) colours
+    "field2d_fd_periodic_64": (dict(kind="matrix", pde="fd", shape=(64, 64), kw=dict(nlevel=4)),
+                               {0: {"sweep": "k_fsweep<2>", "ncolours": 2}}),
+    "field3d_fem_periodic_16": (dict(kind="matrix", pde="fem", shape=(16, 16, 16), kw=dict(nlevel=3)),
+                                {0: {"sweep": "k_fsweep<3>", "ncolours": 8}}),
+    "field2d_squared_32": (H.SWEEP_CASES["m_squared_32"], {0: {"sweep": "k_fsweep<2>", "ncolours": 9}, 1: {"ncolours": 9}}),
+    "field2d_squared_32_periodic": (H.SWEEP_CASES["m_squared_32_periodic"],
+                                    {0: {"sweep": "k_fsweep<2>", "ncolours": 9}, 1: {"ncolours": 9}}),
 }
+NINE_COLOUR_CASES = ["field2d_squared_32", "field2d_squared_32_periodic"]
 
 
 def assert_labels(s, nlevel, labels, name):
+    """key^: a prefix, key$: a suffix; ncolours is the level description's colour count."""
     got = [s.level_kernels(level) for level in range(nlevel)]
     print(f"algebra {name} kernels:", *(";".join(f"{k}={v}" for k, v in d.items()) for d in got), sep="\n  ")
     for level, want in labels.items():
         k = got[level]
         for key, value in want.items():
-            if key.endswith("^"):
+            if key == "ncolours":
+                assert s.level_desc(level)["ncolours"] == value, (name, level, s.level_desc(level))
+            elif key.endswith("^"):
                 assert k.get(key[:-1], "").startswith(value), (name, level, k)
+            elif key.endswith("$"):
+                assert k.get(key[:-1], "").endswith(value), (name, level, k)
             else:
                 assert k.get(key) == value, (name, level, k)
 
@@ -91,11 +127,15 @@ def test_sweeps_are_the_sor_splitting_with_unit_noise(hip_device, name):
     prob = H.problem(case)
     s = prob.sampler(seed=SEED, chain=CHAIN)
     assert_labels(s, prob.params.nlevel, labels, name)
-    ratios = AL.check_sweeps(prob, s, s.normals, TAG, SAMPLE, np.random.default_rng(1),
-                             symmetric=case.get("symmetric", True))
-    s.close()
-    worst = AL.report(name, ratios)
-    assert worst <= AL.C_TOL, ratios
+    las = AL.level_algebras(prob, case.get("symmetric", True))
+    ratios = AL.check_sweeps(prob, s, s.normals, TAG, SAMPLE, np.random.default_rng(1), algebras=las)
+    try:
+        worst = AL.report(name, ratios)
+        assert worst <= AL.C_TOL, ratios
+        if case["kind"] == "matrix":  # R on every level through the device, G on the matrices it is held to
+            H.check_matrix_levels(prob, s, case.get("symmetric", True), name in NINE_COLOUR_CASES, algebras=las)
+    finally:
+        s.close()
 
 
 @pytest.mark.parametrize("pre", [1, 0])
@@ -136,6 +176,13 @@ COMPOSITION_CASES = {
                         3: {"sweep": "k_tail<3>"}, 4: {"sweep": "k_tail<3>"}}),
     "2d_200x120": SWEEP_CASES["2d_200x120"],
     "3d_96x48x48_points": SWEEP_CASES["3d_96x48x48_points"],
+    # matrix handles: the VD level's out-of-place sweeps alternating with the separate prolongation above a field
+    # level, and the 9-colour field levels; SSOR, W-cycles
+    "vd_192x48x40_ssor_W": (dict(kind="matrix", pde="fd", shape=(192, 48, 40),
+                                 kw=dict(nlevel=3, cycle=2, smoother="SSOR", npresmooth=2)), {0: VD, 1: FIELD3}),
+    "field2d_squared_32_ssor_W": (dict(kind="matrix", pde="squared", model="constant", shape=(32, 32),
+                                       kw=dict(nlevel=3, cycle=2, smoother="SSOR")),
+                                  {0: {"sweep": "k_fsweep<2>", "ncolours": 9}}),
 }
 
 

@@ -18,6 +18,11 @@ died".
 Per case: two apply(f, x) cycles with a random f; four prior cycles (f = 0, zero state: the zero-right-hand-side
 instances) with QoI series and final state; for cases marked sweeps the per-level smoother, noisy sweep and
 residual + restriction calls.  Some cases run again with MGMC_POISON=1 (NaN-filled LDS before every launch).
+
+The vd_* cases are matrix handles with a variable-diagonal fine level (a case's "operator" key; the lattices of
+tests/test_gpu_vardiag.py): the VD instance of k_zsweep_rb7 borrows ZS_TYP and ZS_TZ (12 / 16 / 20-row tiles under
+lo / control / hi), and lo's ZR7_WIDE_MIN_TILES = 1 selects k_zresrestrict<7,64,8,512,...,VD>, which the default
+build reaches only at 512^3 and no other test launches.
 """
 import json
 import os
@@ -33,6 +38,7 @@ from tests import oracle_lib as O
 from tests.test_gpu_field_stats import Mirror
 from tests.test_gpu_lowrank import CONFIGS as LR_CONFIGS, measured
 from tests.test_gpu_parity import CONFIGS
+from tests.test_gpu_vardiag import CASES as VD_CASES, build_operator
 from tests.tuning_variants import VARIANTS
 
 pytestmark = pytest.mark.gpu
@@ -43,10 +49,11 @@ KAPPA_SQ = 25.0
 LIBRARIES = ["control"] + list(VARIANTS)
 
 # Wall time of the control child (product library, every case below, interpreter start and library load included)
-# measured on an MI355X: 2.85 s (the lo / hi children: 2.86 / 2.68 s; the slowest case, depth_hi, 0.41 s).  A
+# measured on an MI355X: 3.70 s (the lo / hi children: 3.66 / 3.65 s; the slowest case, depth_hi, 0.42 s; the
+# eight vd_* cases together 0.96 s, of which the first, vd_A, 0.24 s and the three-level vd_C 0.27 s).  A
 # child's limit is 5 x that (spilled or tiny-tile variants and first-use code-object loads are slower); a child that
 # exceeds it counts as hung.
-CONTROL_SECONDS = 2.85
+CONTROL_SECONDS = 3.70
 CHILD_TIMEOUT = 5 * CONTROL_SECONDS
 
 # ---- the z-chunk depth cases ----
@@ -73,10 +80,21 @@ def depth_shape(variant):
 
 
 def _case(cid, shape, params, *, disable="", poison=False, nchains=1, sweeps=False, measurements=None,
-          field_stats=0, oracle=None):
+          field_stats=0, oracle=None, operator=None, lowrank=False):
+    """operator: None (the FD prior, kappa^2 = 25) or a matrix handle's, "fd_periodic" | "dominant"
+    (tests/test_gpu_vardiag.build_operator; lowrank: with its three point measurements and the global average)."""
     return {"id": cid + ("-poison" if poison else ""), "shape": list(shape), "params": params, "disable": disable,
             "poison": poison, "nchains": nchains, "chain0": 0 if nchains == 1 else 11, "sweeps": sweeps,
-            "measurements": measurements, "field_stats": field_stats, "oracle": oracle or cid}
+            "measurements": measurements, "field_stats": field_stats, "oracle": oracle or cid,
+            "operator": operator, "lowrank": lowrank}
+
+
+def _vardiag(name, *, suffix="", **kw):
+    """A lattice of tests/test_gpu_vardiag.py (A .. D) as a matrix handle: the VD instances of k_zsweep_rb7 (which
+    borrow ZS_TYP and ZS_TZ) and of k_zresrestrict<7, ...> (ZR7_WIDE_MIN_TILES) under the variants."""
+    shape, params = VD_CASES[name]
+    cid = f"vd_{name}{suffix}" + (f"-k{kw['nchains']}" if kw.get("nchains") else "")
+    return _case(cid, shape, params, operator="dominant" if name == "D" else "fd_periodic", oracle=cid, **kw)
 
 
 def _prior(name, **kw):
@@ -122,7 +140,12 @@ CASES = (
     # elsewhere): tests/test_tuning_host.py asserts it from jsweep_plan_dims, the function launch_jsweep calls, for 256
     # compute units, and test_jsweep_rounds_case_is_sized_for_the_device checks the device's count against it
     [_case("3d_jsweep_rounds", (512, 116, 116), dict(nlevel=3))] +
-    [_prior(name, poison=True, **kw) for name, kw in POISONED])
+    # matrix handles with a variable-diagonal fine level: no other case runs a VD kernel through a variant, and the
+    # default build reaches the 512-thread k_zresrestrict<7,64,8,...,VD> only at 512^3
+    [_vardiag("A", sweeps=True), _vardiag("B", sweeps=True), _vardiag("C"), _vardiag("D"), _vardiag("B", nchains=3),
+     _vardiag("B", suffix="_lowrank", lowrank=True)] +
+    [_prior(name, poison=True, **kw) for name, kw in POISONED] +
+    [_vardiag("A", sweeps=True, poison=True), _vardiag("C", poison=True)])
 CASE_IDS = [c["id"] for c in CASES]
 assert len(set(CASE_IDS)) == len(CASE_IDS)
 
@@ -205,6 +228,20 @@ LABELS = {
                                   for lib in LIBRARIES},
     "lr_3d_96x48x48_points": {lib: [(1, "sweep", "k_sweep_quads<3>"), (1, "quads", "window")] for lib in LIBRARIES},
 }
+# the VD instances: the sweep's tile is the variant's ZS_TYP, the 7-point restriction the 512-thread 64 x 8 instance
+# under lo (ZR7_WIDE_MIN_TILES 1), which the default build selects only at 512^3 and no other test launches
+_VD_ROWS = {"control": 16, "lo": VARIANTS["lo"]["ZS_TYP"], "hi": VARIANTS["hi"]["ZS_TYP"]}
+_VD_RES = {"control": "k_zresrestrict<7,64,4>", "lo": "k_zresrestrict<7,64,8>", "hi": "k_zresrestrict<7,64,4>"}
+assert _VD_ROWS == {"control": 16, "lo": 12, "hi": 20}
+for _c in CASES:
+    if _c["operator"] and not _c["poison"]:
+        LABELS[_c["id"]] = {
+            lib: [(0, "sweep", f"k_zsweep_rb7<32,{_VD_ROWS[lib]},...,0,VD>"), (0, "residual_restrict", _VD_RES[lib]),
+                  (0, "diag", "field"), (0, "post_sweep", None), (0, "rhs", None), (0, "tz", "8")] +
+                 ([(1, "sweep", "k_fsweep<3>"), (1, "residual_restrict", "k_fresidual + k_restrict"), (1, "diag", None)]
+                  if _c["params"]["nlevel"] > 2 else [])
+            for lib in LIBRARIES}
+        LABELS[_c["id"] + "-poison"] = LABELS[_c["id"]]
 for _v in VARIANTS:  # a variant's own depth case keeps its ZS_TZ / ZS_TZP; every smaller z-sweep case ends at 8 / 8
     LABELS[f"depth_{_v}"] = {_v: [(0, "tz", _tz(_v, True))]}
 for _name, _ in POISONED:  # the poisoned runs select what the plain ones do
@@ -219,6 +256,14 @@ def _parameters(case):
 
 def _oracle(case, chain):
     p = _parameters(case)
+    if case["operator"]:  # the replay of the matrix the worker hands to mgmc_create_csr
+        op, _ = build_operator(tuple(case["shape"]), case["operator"] == "dominant", case["lowrank"])
+        rowptr, col, val = getattr(op, "base_operator", op).get_csr()
+        mc = O.Oracle.csr(tuple(case["shape"]), p, rowptr, col, val, mode=O.MULTICOLOUR, seed=SEED)
+        mc.reseed(SEED, chain)
+        if case["lowrank"]:
+            mc.set_lowrank(op.get_B())
+        return mc, p
     mc = O.Oracle.fd_own(tuple(case["shape"]), p, KAPPA_SQ, mode=O.MULTICOLOUR, seed=SEED, chain=chain)
     if case["measurements"] is not None:
         op, _ = measured(tuple(case["shape"]), KAPPA_SQ, *case["measurements"])
@@ -344,7 +389,8 @@ def tuning_results(hip_device, tmp_path_factory):
                 done[case["oracle"]] = dict(case)
             # cases that share expected arrays must ask for the same ones
             assert all(done[case["oracle"]][key] == case[key] for key in ("shape", "params", "nchains", "chain0",
-                                                                          "measurements", "field_stats"))
+                                                                          "measurements", "field_stats", "operator",
+                                                                          "lowrank"))
             case["dir"] = directory
     finally:
         O.set_threads(1)
@@ -390,7 +436,9 @@ def test_tuning_variant_bitwise(tuning_results, library, case_id):
     # (every z-sweep case below the depth cases' size ends at 8 / 8; 3d_jsweep_rounds, 6.9 M unknowns, is sized for
     # its level 1 and keeps deeper chunks)
     if r["labels"][0]["sweep"].startswith("k_zsweep_rb7") and not case_id.startswith(("depth_", "3d_jsweep_rounds")):
-        assert r["labels"][0]["tz"] == "8/8", (case_id, r["labels"][0])
+        # (the VD instance is the plain sweep only: its label carries one depth)
+        want = "8" if r["labels"][0].get("diag") == "field" else "8/8"
+        assert r["labels"][0]["tz"] == want, (case_id, r["labels"][0])
 
 
 @pytest.mark.parametrize("variant", list(VARIANTS))

@@ -16,9 +16,13 @@ the CPU oracle's MULTICOLOUR replay of the same matrix, which the field kernels 
   B     128x34x18    nlevel 2, omega 0.9, coarse_scaling 0.9: the smallest z-sweep algebra shape
   C     192x48x40    nlevel 3, SSOR, 2 pre-sweeps, W-cycle: nx no multiple of 128, field coarse levels
   D     128x34x18    a hand-made matrix, cx != cy != cz and a random dominant diagonal: a coefficient mix-up shows
+  E     128x18x3042  nlevel 2: z-chunks of 32 planes on 256 compute units, as at 256^3 (test_deep_chunks_bitwise)
+  A_p_q, C_sor_W     A's lattice with (npresmooth, npostsmooth) = (0, 1), (1, 0), (0, 0), (3, 2); C's with a SOR
+                     W-cycle (test_cycle_shapes_bitwise)
 
 Measured on MI355X (test_sweep_against_the_red_black_relation, case B): worst ratio 2.93 forward, 3.07
-backward, against C_TOL = 8."""
+backward, against C_TOL = 8.  Case E reports tz=32 on the MI355X's 256 compute units; its test takes 8.5 s, nearly
+all of it the host's assembly, Galerkin product and the oracle's replay of 6.6 M unknowns (16 threads)."""
 import functools
 
 import numpy as np
@@ -39,7 +43,17 @@ CASES = {
     "B": ((128, 34, 18), dict(nlevel=2, omega=0.9, coarse_scaling=0.9)),
     "C": ((192, 48, 40), dict(nlevel=3, smoother="SSOR", npresmooth=2, cycle=2)),
     "D": ((128, 34, 18), dict(nlevel=2)),
+    # the z-chunk depth of the 256^3 workload (test_deep_chunks_bitwise)
+    "E": ((128, 18, 3042), dict(nlevel=2)),
+    # cycle shapes (test_cycle_shapes_bitwise): A's and C's lattices
+    "A_0_1": ((64, 22, 10), dict(nlevel=2, npresmooth=0, npostsmooth=1)),
+    "A_1_0": ((64, 22, 10), dict(nlevel=2, npresmooth=1, npostsmooth=0)),
+    "A_0_0": ((64, 22, 10), dict(nlevel=2, npresmooth=0, npostsmooth=0)),
+    "A_3_2": ((64, 22, 10), dict(nlevel=2, npresmooth=3, npostsmooth=2)),
+    "C_sor_W": ((192, 48, 40), dict(nlevel=3, cycle=2)),
 }
+SMALL = ["A", "B", "C", "D"]
+SHAPES = ["A_0_1", "A_1_0", "A_0_0", "A_3_2", "C_sor_W"]
 FIELD_SWEEP, FIELD_RES = "k_fsweep<3>", "k_fresidual + k_restrict"
 
 
@@ -48,9 +62,14 @@ def params(name):
 
 
 def operator(name, lowrank=False):
-    shape = CASES[name][0]
+    return build_operator(CASES[name][0], name == "D", lowrank)
+
+
+def build_operator(shape, dominant=False, lowrank=False):
+    """(operator, lattice): the periodic-kappa^2 FD operator or the hand-made dominant matrix on `shape` cells (also
+    what tests/tuning_worker.py and tests/test_gpu_tuning.py build for their variable-diagonal cases)."""
     lat = mg.Lattice(*shape)
-    op = mg.SparseMatrixOperator(lat, dominant_matrix(shape)) if name == "D" else mg.ShiftedLaplaceFDOperator(lat, PERIODIC)
+    op = mg.SparseMatrixOperator(lat, dominant_matrix(shape)) if dominant else mg.ShiftedLaplaceFDOperator(lat, PERIODIC)
     if lowrank:  # 3 point measurements and the global average, as test_gpu_varcoef.make(lowrank=True)
         rng = np.random.default_rng(3)
         mp = MeasurementParameters(radius=0.0, variance_scaling=1e-3, measure_global=True, variance_global=0.02)
@@ -151,7 +170,7 @@ def assert_fast_labels(s):
 
 
 # 1
-@pytest.mark.parametrize("name", list(CASES))
+@pytest.mark.parametrize("name", SMALL)
 def test_labels(hip_device, name):
     s, lat = sampler(name)
     assert_fast_labels(s)
@@ -164,7 +183,7 @@ def test_labels(hip_device, name):
 
 
 # 2
-@pytest.mark.parametrize("name", list(CASES))
+@pytest.mark.parametrize("name", SMALL)
 def test_components_bitwise(hip_device, name):
     s, lat = sampler(name)
     assert_fast_labels(s)
@@ -173,7 +192,7 @@ def test_components_bitwise(hip_device, name):
 
 
 # 3
-@pytest.mark.parametrize("name,zero", [(n, False) for n in CASES] + [("A", True), ("B", True)])
+@pytest.mark.parametrize("name,zero", [(n, False) for n in SMALL] + [("A", True), ("B", True)])
 def test_cycles_bitwise(hip_device, name, zero):
     s, lat = sampler(name)
     check_cycles(s, lat, name, zero)
@@ -281,3 +300,59 @@ def test_sweep_against_the_red_black_relation(hip_device):
           % (worst[mg.FORWARD], worst[mg.BACKWARD]))
     assert max(worst.values()) <= AL.C_TOL, worst
     s.close()
+
+
+def assert_same(got, ref, what):
+    bad = np.flatnonzero(got != ref)
+    assert got.shape == ref.shape and bad.size == 0, \
+        f"{what}: {bad.size} of {ref.size} values differ, first at {bad[:1]}, last at {bad[-1:]}"
+
+
+# 9
+def test_deep_chunks_bitwise(hip_device):
+    """Case E, 128 x 18 x 3042: the smallest lattice on which the VD sweep keeps the z-chunk depth ZS_TZ = 32 of the
+    256^3 workload on 256 compute units (zsweep_depth halves it while 4 tiles_xy nchunks < 6 num_cu): two x tiles, a
+    full and a one-row y tile of ZS_TYP = 16 rows, 96 chunks of which the last is a single plane -- 4 * 4 * 96 =
+    1536 = 3 * 2 * 256.  Every other VD case of the suite runs 8-plane chunks.  Noisy sweeps, the smoother, the
+    residual + restriction and one cycle, bit for bit against the oracle."""
+    from tests.tuning_worker import num_cu
+    name = "E"
+    s, lat = sampler(name)
+    O.set_threads(min(16, O.cpu_share()))
+    try:
+        assert_fast_labels(s)
+        k0 = s.level_kernels(0)
+        assert k0["tz"] == "32", f"{k0}: the lattice is sized for 256 compute units, the device reports {num_cu()}"
+        mc = oracle(name)
+        x, b = component_inputs(name)
+        for d in (mg.FORWARD, mg.BACKWARD):
+            assert_same(s.sor_sampler_apply(0, d, 3, 19, b, x), mc.sor_sampler_apply(0, d, 3, 19, b, x), f"sampler {d}")
+            assert_same(s.smoother_apply(0, d, 2, b, x), mc.smoother_apply(0, d, 2, b, x), f"smoother {d}")
+        assert_same(s.residual_restrict(0, b, x), mc.residual_restrict(0, b, x), "residual + restriction")
+        f = rhs(name, False)
+        got, ref = np.zeros(lat.Nvertex), np.zeros(lat.Nvertex)
+        s.apply(f, got)
+        mc.apply(f, ref)
+        assert_same(got, ref, "one cycle")
+    finally:
+        O.set_threads(1)
+        s.close()
+
+
+# 10
+@pytest.mark.parametrize("name", SHAPES)
+def test_cycle_shapes_bitwise(hip_device, name):
+    """A VD level has no fused prolongation and is never rhs=zero: its out-of-place sweeps (x -> x2) alternate with
+    a separate prolongation, so the buffer a cycle ends in depends on the sweep counts.  (npresmooth, npostsmooth)
+    = (0, 1), (1, 0), (0, 0), (3, 2) on A's lattice and a SOR W-cycle above a field level on C's: two cycles and a
+    5-sample series."""
+    s, lat = sampler(name)
+    try:
+        assert_fast_labels(s)
+        check_cycles(s, lat, name)
+        assert_fast_labels(s)
+        if s.nlevel > 2:
+            k1 = s.level_kernels(1)
+            assert k1["sweep"] == FIELD_SWEEP and k1["residual_restrict"] == FIELD_RES, k1
+    finally:
+        s.close()

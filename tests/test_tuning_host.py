@@ -62,10 +62,10 @@ def plan_programs(tmp_path_factory):
     return exes
 
 
-def plan(exe, shape, nlevel, disable=""):
+def plan(exe, shape, nlevel, disable="", vardiag=False):
     nx, ny, nz = (list(shape) + [0])[:3]
-    r = subprocess.run([exe, "plan", str(nx), str(ny), str(nz), str(nlevel), disable], capture_output=True, text=True,
-                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    r = subprocess.run([exe, "plan", str(nx), str(ny), str(nz), str(nlevel), disable] + (["vardiag"] if vardiag else []),
+                       capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
     assert r.returncode == 0, r.stdout + r.stderr
     return r.stdout.splitlines()
 
@@ -128,6 +128,31 @@ PLANS = [
 def test_variant_selects_the_instance(plan_programs, header, shape, nlevel, disable, level, want):
     line = plan(plan_programs[header], shape, nlevel, disable)[level]
     assert line.startswith(f"level {level} ") and want in line, line
+
+
+# The matrix handle of a variable-diagonal fine level (the vd_* cases of tests/test_gpu_tuning.py, the lattices of
+# tests/test_gpu_vardiag.py): the VD sweep takes the variant's ZS_TYP rows, the 7-point restriction the 512-thread
+# 64 x 8 instance under lo only -- by default only from 16,384 wide tiles up (512^3) -- and level 1 the field kernels.
+VD_LEVEL0 = {"default": "sweep ZSWEEP rows 16 residual ZMARCH np 7 cx 64 cy 4 nt 256 vd tail -1",
+             "lo": "sweep ZSWEEP rows 12 residual ZMARCH np 7 cx 64 cy 8 nt 512 vd tail -1",
+             "hi": "sweep ZSWEEP rows 20 residual ZMARCH np 7 cx 64 cy 4 nt 256 vd tail -1"}
+VD_SHAPES = [((64, 22, 10), 2), ((128, 34, 18), 2), ((192, 48, 40), 3)]
+
+
+@pytest.mark.parametrize("header", list(VD_LEVEL0))
+@pytest.mark.parametrize("shape,nlevel", VD_SHAPES, ids=["x".join(map(str, s)) for s, _ in VD_SHAPES])
+def test_variant_selects_the_vardiag_instances(plan_programs, header, shape, nlevel):
+    lines = plan(plan_programs[header], shape, nlevel, vardiag=True)
+    assert lines[0] == "level 0 " + VD_LEVEL0[header], lines
+    if nlevel > 2:
+        assert lines[1] == "level 1 sweep FIELD residual FIELD tail -1", lines
+    # the default header reaches the wide instance at 512^3 only (256^3: 4,064 wide tiles)
+    if header == "default":
+        assert "cy 8 nt 512 vd" in plan(plan_programs[header], (512, 512, 512), 2, vardiag=True)[0]
+        assert "cy 4 nt 256 vd" in plan(plan_programs[header], (256, 256, 256), 2, vardiag=True)[0]
+    # MGMC_DISABLE=zsweep leaves the level to the field kernels under every header
+    assert plan(plan_programs[header], shape, nlevel, "zsweep", vardiag=True)[0] == \
+        "level 0 sweep FIELD residual FIELD tail -1"
 
 
 def _hierarchy(shape, nlevel):

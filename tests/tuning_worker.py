@@ -84,7 +84,11 @@ def make_sampler(case):
         else:
             os.environ.pop(key, None)
     lat = mg.Lattice(*case["shape"])
-    if case["measurements"] is not None:
+    if case.get("operator"):  # a matrix handle with a variable-diagonal fine level: "fd_periodic" | "dominant"
+        from tests.test_gpu_vardiag import build_operator
+        assert case["operator"] in ("fd_periodic", "dominant") and case["measurements"] is None
+        op, lat = build_operator(tuple(case["shape"]), case["operator"] == "dominant", case.get("lowrank", False))
+    elif case["measurements"] is not None:
         from tests.test_gpu_lowrank import measured
         op, lat = measured(tuple(case["shape"]), KAPPA_SQ, *case["measurements"])
     else:
