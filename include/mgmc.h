@@ -344,6 +344,30 @@ int mgmc_field_stats_info(const mgmc_handle* h, int* enabled, int* stride, uint6
 int mgmc_field_stats_get(mgmc_handle* h, double* mean, double* m2, size_t n);
                                                           /* reference layout, n = ndof; either pointer may be NULL;
                                                              waits for the handle's stream */
+/* Batch means: the Monte Carlo error of the mean field and the integrated autocorrelation time per vertex
+ * (the reference's Statistics class estimates tau_int of one series from its autocovariances,
+ * auxilliary/statistics.cc).  With batch length B, in recorded cycles r = 1, 2, ... since the enable / reset,
+ * three more fields: bsum, the sum of the current batch, and bmean / bM2, the Welford mean and M2 of the
+ * completed batches' means.  On recorded cycle r, besides the update above and with its chain order:
+ *     bsum += x_c (c = 0 .. nchains-1);  if r % B == 0:  bm = bsum / (double)(B * nchains);  nb = r / B;
+ *     d = bm - bmean;  bmean += d / nb;  bM2 += d * (bm - bmean);  bsum = +0.0.
+ * A batch pools the chains of its B cycles.  With nb completed batches the standard error of the mean field
+ * is sqrt(bM2 / (nb - 1) / nb) and tau = B * nchains * (bM2 / (nb - 1)) / (M2 / (nrecorded - 1)).  mean and
+ * M2 are bitwise what they are without batching.  mgmc_field_stats_reset zeroes the three fields too and
+ * drops a partial batch; mgmc_set_lowrank and mgmc_set_qoi_vector keep a partial batch; disable, info and
+ * get work as above.  mgmc_field_stats_enable on a batched handle frees the three fields, rebuilds the
+ * graphs and resets.  MGMC_E_INVALID: stride < 1, batch < 1, a wrong n, get_batch while batching is off;
+ * MGMC_E_NOMEM: the fields could not be allocated (the handle stays as it was before the call). */
+int mgmc_field_stats_enable_batched(mgmc_handle* h, int stride, int batch);
+                                                          /* stride, batch >= 1; allocates + zeroes five fields,
+                                                             rebuilds graphs; on a batched handle: reset with the
+                                                             new stride and batch (same graphs) */
+int mgmc_field_stats_batch_info(const mgmc_handle* h, int* batch, uint64_t* nbatches);
+                                                          /* batch = 0 without batching or disabled; nbatches =
+                                                             completed batches */
+int mgmc_field_stats_get_batch(mgmc_handle* h, double* bmean, double* bm2, size_t n);
+                                                          /* reference layout, n = ndof; either pointer may be NULL;
+                                                             waits for the handle's stream */
 
 /* ---- component entry points (host buffers, reference layout) used by the parity tests ---- */
 /* y = Q_level x  (LinearOperator::apply; Q = A + B Sigma^{-1} B^T once mgmc_set_lowrank ran) */

@@ -151,6 +151,28 @@ class HipMultigridMCSampler {
     void field_stats(int stride = 1) {
         check(mgmc_field_stats_enable(h_.get(), stride), h_.get(), "mgmc_field_stats_enable");
     }
+    // the same with batch means of `batch` recorded cycles (mgmc_field_stats_enable_batched): the Monte
+    // Carlo error of the mean field and the integrated autocorrelation time per vertex
+    void field_stats(int stride, int batch) {
+        check(mgmc_field_stats_enable_batched(h_.get(), stride, batch), h_.get(), "mgmc_field_stats_enable_batched");
+    }
+    // batch length (0 without batching or while disabled)
+    int field_batch() const {
+        int b = 0;
+        check(mgmc_field_stats_batch_info(h_.get(), &b, nullptr), h_.get(), "mgmc_field_stats_batch_info");
+        return b;
+    }
+    // completed batches
+    uint64_t field_batches() const {
+        uint64_t nb = 0;
+        check(mgmc_field_stats_batch_info(h_.get(), nullptr, &nb), h_.get(), "mgmc_field_stats_batch_info");
+        return nb;
+    }
+    // mean and M2 of the completed batches' means in the reference layout (either may be nullptr): with
+    // nb = field_batches() >= 2 the standard error of the mean field is sqrt(bm2 / (nb - 1) / nb)
+    void field_batch_moments(double* bmean, double* bm2) const {
+        check(mgmc_field_stats_get_batch(h_.get(), bmean, bm2, ndof_), h_.get(), "mgmc_field_stats_get_batch");
+    }
     void field_stats_off() { check(mgmc_field_stats_disable(h_.get()), h_.get(), "mgmc_field_stats_disable"); }
     void reset_field_stats() { check(mgmc_field_stats_reset(h_.get()), h_.get(), "mgmc_field_stats_reset"); }
     // states folded in so far (recorded cycles x nchains); 0 while disabled

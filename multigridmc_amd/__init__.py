@@ -26,6 +26,7 @@ from .sampler import (  # noqa: F401
     SSORSmootherFactory,
     ConstantCorrelationLengthModel,
     PeriodicCorrelationLengthModel,
+    batch_means_estimates,
     comm_unique_id,
     csr_colour_scheme,
     describe,

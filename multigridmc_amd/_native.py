@@ -127,6 +127,9 @@ SIGNATURES = [
     ("mgmc_field_stats_reset", c_int, [_H]),
     ("mgmc_field_stats_info", c_int, [_H, POINTER(c_int), POINTER(c_int), POINTER(c_uint64)]),
     ("mgmc_field_stats_get", c_int, [_H, _DP, _DP, c_size_t]),
+    ("mgmc_field_stats_enable_batched", c_int, [_H, c_int, c_int]),
+    ("mgmc_field_stats_batch_info", c_int, [_H, POINTER(c_int), POINTER(c_uint64)]),
+    ("mgmc_field_stats_get_batch", c_int, [_H, _DP, _DP, c_size_t]),
     ("mgmc_operator_apply", c_int, [_H, c_int, _DP, _DP]),
     ("mgmc_smoother_apply", c_int, [_H, c_int, c_int, c_int, _DP, _DP]),
     ("mgmc_sor_smoother_apply", c_int, [_H, c_int, c_int, c_int, _DP, _DP]),

@@ -1912,7 +1912,7 @@ void enqueue_ops(mgmc_handle* h, size_t begin, size_t end, hipStream_t s) {
             }
             case OP_FIELDSTATS: {  // level 0's canonical buffer holds the cycle's state (OP_COPY before OP_QOI)
                 launch_fieldstats(h->levels[0].x, (long long)h->levels[0].L.nstore, nch, h->fs_mean, h->fs_m2,
-                                  h->fs_ctl, s);
+                                  h->fs_ctl, s, h->fs_bsum, h->fs_bmean, h->fs_bm2);
                 break;
             }
         }
@@ -2687,6 +2687,9 @@ int mgmc_destroy(mgmc_handle* h) {
     if (h->fs_mean) hipFree(h->fs_mean);
     if (h->fs_m2) hipFree(h->fs_m2);
     if (h->fs_ctl) hipFree(h->fs_ctl);
+    if (h->fs_bsum) hipFree(h->fs_bsum);
+    if (h->fs_bmean) hipFree(h->fs_bmean);
+    if (h->fs_bm2) hipFree(h->fs_bm2);
     if (h->stream) hipStreamDestroy(h->stream);
     delete h;
     return MGMC_OK;
@@ -3379,16 +3382,31 @@ int mgmc_sample_timed_stride(mgmc_handle* h, int nsteps, int stride, int64_t qoi
 
 // ---------------- pointwise field statistics (mgmc_fieldstats.hpp; driver_mgmc.cc:118-171) ----------------
 
-// zero both fields and the counters, keep (or set) the stride; on the handle's stream
-static int fieldstats_zero(mgmc_handle* h, int stride) {
+// zero the fields (the batch fields too, where they exist) and the counters, keep (or set) the stride and
+// the batch length; on the handle's stream
+static int fieldstats_zero(mgmc_handle* h, int stride, int batch) {
     const size_t bytes = (size_t)h->levels[0].L.nstore * sizeof(double);
-    const uint64_t ctl0[FS_CTL_WORDS] = {0, 0, (uint64_t)stride, 0};
+    const uint64_t ctl0[FS_CTL_WORDS] = {0, 0, (uint64_t)stride, (uint64_t)batch};
     HIPCHK(h, hipMemsetAsync(h->fs_mean, 0, bytes, h->stream));
     HIPCHK(h, hipMemsetAsync(h->fs_m2, 0, bytes, h->stream));
+    if (h->fs_bsum) {
+        HIPCHK(h, hipMemsetAsync(h->fs_bsum, 0, bytes, h->stream));
+        HIPCHK(h, hipMemsetAsync(h->fs_bmean, 0, bytes, h->stream));
+        HIPCHK(h, hipMemsetAsync(h->fs_bm2, 0, bytes, h->stream));
+    }
     HIPCHK(h, hipMemcpyAsync(h->fs_ctl, ctl0, sizeof(ctl0), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));  // (ctl0 is on this stack)
     h->fs_stride = stride;
+    h->fs_batch = batch;
     return MGMC_OK;
+}
+
+static void fieldstats_free_batch(mgmc_handle* h) {
+    if (h->fs_bsum) hipFree(h->fs_bsum);
+    if (h->fs_bmean) hipFree(h->fs_bmean);
+    if (h->fs_bm2) hipFree(h->fs_bm2);
+    h->fs_bsum = h->fs_bmean = h->fs_bm2 = nullptr;
+    h->fs_batch = 0;
 }
 
 static void fieldstats_free(mgmc_handle* h) {
@@ -3398,6 +3416,26 @@ static void fieldstats_free(mgmc_handle* h) {
     h->fs_mean = h->fs_m2 = nullptr;
     h->fs_ctl = nullptr;
     h->fs_stride = 0;
+    fieldstats_free_batch(h);
+}
+
+// the fields are allocated: zero them, put the op in and capture the graphs; on an error back to the
+// cycle without the op
+static int fieldstats_start(mgmc_handle* h, int stride, int batch) {
+    int rc = fieldstats_zero(h, stride, batch);
+    if (rc == MGMC_OK) {
+        sync_fieldstats_op(h);
+        rc = build_graphs(h);
+    }
+    if (rc != MGMC_OK) {
+        const std::string err = h->last_error;
+        destroy_graphs(h);
+        fieldstats_free(h);
+        sync_fieldstats_op(h);
+        (void)build_graphs(h);
+        return fail(h, rc, err);
+    }
+    return MGMC_OK;
 }
 
 int mgmc_field_stats_enable(mgmc_handle* h, int stride) {
@@ -3405,7 +3443,12 @@ int mgmc_field_stats_enable(mgmc_handle* h, int stride) {
     if (stride < 1) return fail(h, MGMC_E_INVALID, "field statistics: stride must be >= 1");
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->fs_mean) return fieldstats_zero(h, stride);  // enabled: a reset with the new stride (same graphs)
+    if (h->fs_bsum) {  // batched: back to the kernel without batching (the graphs hold the batch fields' addresses)
+        destroy_graphs(h);
+        fieldstats_free_batch(h);
+        return fieldstats_start(h, stride, 0);
+    }
+    if (h->fs_mean) return fieldstats_zero(h, stride, 0);  // enabled: a reset with the new stride (same graphs)
     const size_t bytes = (size_t)h->levels[0].L.nstore * sizeof(double);
     if (hipMalloc(&h->fs_mean, bytes) != hipSuccess || hipMalloc(&h->fs_m2, bytes) != hipSuccess ||
         hipMalloc(&h->fs_ctl, FS_CTL_WORDS * sizeof(uint64_t)) != hipSuccess) {
@@ -3413,19 +3456,41 @@ int mgmc_field_stats_enable(mgmc_handle* h, int stride) {
         fieldstats_free(h);  // disabled, otherwise intact: the op list and the graphs were not touched
         return fail(h, MGMC_E_NOMEM, "device allocation failed (field statistics)");
     }
-    int rc = fieldstats_zero(h, stride);
-    if (rc == MGMC_OK) {
-        sync_fieldstats_op(h);
-        rc = build_graphs(h);
+    return fieldstats_start(h, stride, 0);
+}
+
+int mgmc_field_stats_enable_batched(mgmc_handle* h, int stride, int batch) {
+    if (!h) return fail(nullptr, MGMC_E_INVALID, "null handle");
+    if (stride < 1) return fail(h, MGMC_E_INVALID, "field statistics: stride must be >= 1");
+    if (batch < 1) return fail(h, MGMC_E_INVALID, "field statistics: batch must be >= 1");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (h->fs_bsum) return fieldstats_zero(h, stride, batch);  // batched: a reset with both (same graphs)
+    // the fields the handle lacks: all five and the counters, or the three batch fields of an enabled handle;
+    // the handle takes them only once all are there
+    const size_t bytes = (size_t)h->levels[0].L.nstore * sizeof(double);
+    const bool enabled = h->fs_mean != nullptr;
+    double* f[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    uint64_t* ctl = nullptr;
+    bool ok = true;
+    for (int q = enabled ? 2 : 0; q < 5 && ok; ++q) ok = hipMalloc(&f[q], bytes) == hipSuccess;
+    if (ok && !enabled) ok = hipMalloc(&ctl, FS_CTL_WORDS * sizeof(uint64_t)) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        for (double* p : f)
+            if (p) hipFree(p);
+        if (ctl) hipFree(ctl);
+        return fail(h, MGMC_E_NOMEM, "device allocation failed (field statistics, batch means)");
     }
-    if (rc != MGMC_OK) {  // back to the cycle without the op
-        const std::string err = h->last_error;
-        fieldstats_free(h);
-        sync_fieldstats_op(h);
-        (void)build_graphs(h);
-        return fail(h, rc, err);
+    if (!enabled) {
+        h->fs_mean = f[0];
+        h->fs_m2 = f[1];
+        h->fs_ctl = ctl;
     }
-    return MGMC_OK;
+    h->fs_bsum = f[2];
+    h->fs_bmean = f[3];
+    h->fs_bm2 = f[4];
+    return fieldstats_start(h, stride, batch);
 }
 
 int mgmc_field_stats_disable(mgmc_handle* h) {
@@ -3443,7 +3508,7 @@ int mgmc_field_stats_reset(mgmc_handle* h) {
     if (!h) return fail(nullptr, MGMC_E_INVALID, "null handle");
     if (!h->fs_mean) return fail(h, MGMC_E_INVALID, "field statistics are not enabled (mgmc_field_stats_enable)");
     HIPCHK(h, hipSetDevice(h->device));
-    return fieldstats_zero(h, h->fs_stride);
+    return fieldstats_zero(h, h->fs_stride, h->fs_batch);
 }
 
 int mgmc_field_stats_info(const mgmc_handle* h, int* enabled, int* stride, uint64_t* nrecorded) {
@@ -3470,6 +3535,36 @@ int mgmc_field_stats_get(mgmc_handle* h, double* mean, double* m2, size_t n) {
     int rc = MGMC_OK;
     if (mean && (rc = download(h, 0, h->fs_mean, mean))) return rc;
     if (m2 && (rc = download(h, 0, h->fs_m2, m2))) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MGMC_OK;
+}
+
+int mgmc_field_stats_batch_info(const mgmc_handle* h, int* batch, uint64_t* nbatches) {
+    if (!h) return fail(nullptr, MGMC_E_INVALID, "null handle");
+    if (batch) *batch = h->fs_batch;
+    if (nbatches) {
+        *nbatches = 0;
+        if (h->fs_bsum) {  // recorded cycles = states recorded / nchains
+            uint64_t nrec = 0;
+            if (hipSetDevice(h->device) != hipSuccess ||
+                hipMemcpyAsync(&nrec, h->fs_ctl + 1, sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+                hipStreamSynchronize(h->stream) != hipSuccess)
+                return fail(nullptr, MGMC_E_HIP, "field statistics: reading the counter failed");
+            *nbatches = nrec / (uint64_t)h->nchains / (uint64_t)h->fs_batch;
+        }
+    }
+    return MGMC_OK;
+}
+
+int mgmc_field_stats_get_batch(mgmc_handle* h, double* bmean, double* bm2, size_t n) {
+    if (!h) return fail(nullptr, MGMC_E_INVALID, "null handle");
+    if (!h->fs_bsum)
+        return fail(h, MGMC_E_INVALID, "field statistics: batch means are not enabled (mgmc_field_stats_enable_batched)");
+    if (n != h->levels[0].spec.ndof) return fail(h, MGMC_E_INVALID, "field statistics size mismatch");
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = MGMC_OK;
+    if (bmean && (rc = download(h, 0, h->fs_bmean, bmean))) return rc;
+    if (bm2 && (rc = download(h, 0, h->fs_bm2, bm2))) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return MGMC_OK;
 }

@@ -253,8 +253,13 @@ struct mgmc_handle {
     // pointwise field statistics (mgmc_field_stats_*, mgmc_fieldstats.hpp): enabled <=> fs_mean != nullptr
     double* fs_mean = nullptr;      // running mean and M2 per stored vertex of level 0, pooled over the chains
     double* fs_m2 = nullptr;
-    uint64_t* fs_ctl = nullptr;     // [0] cycles seen [1] states recorded [2] stride
+    uint64_t* fs_ctl = nullptr;     // [0] cycles seen [1] states recorded [2] stride [3] batch length
     int fs_stride = 0;
+    // batch means (mgmc_field_stats_enable_batched): on <=> fs_bsum != nullptr (then fs_mean != nullptr too)
+    double* fs_bsum = nullptr;      // sum of the current batch
+    double* fs_bmean = nullptr;     // Welford mean and M2 of the completed batches' means
+    double* fs_bm2 = nullptr;
+    int fs_batch = 0;               // batch length in recorded cycles (0: no batching)
     std::string last_error;
     ncclComm_t comm = nullptr;
     int nranks = 1, rank = 0;

@@ -210,24 +210,30 @@ def measure_convergence(sampler, exact: ExactTargets, sampling_params: SamplingP
 
 
 def posterior_statistics(sampler, exact: ExactTargets, sampling_params: SamplingParameters,
-                         measurement_params: MeasurementParameters):
+                         measurement_params: MeasurementParameters, stderr_batch=None):
     """driver_mgmc.cc:118-171: the sample mean and the pointwise variance of the field over nsamples
     cycles after nwarmup, to posterior.vtk with the exact mean (2D: the sample location's circle to
     sample_location.vtk).  The moments are accumulated on the device (field_stats): the state never
-    leaves HBM."""
+    leaves HBM.  stderr_batch=B (--stderr-batch B): batch means of B cycles on the device too, and
+    posterior.vtk also carries mean_stderr, the Monte Carlo standard error of the mean field, and iact, the
+    integrated autocorrelation time per vertex; nsamples must hold at least two batches."""
     op = sampler.get_linear_operator()
     y = _measured_values(measurement_params)
     mean_x_exact = exact.posterior_mean(y) if op.get_m_lowrank() > 0 else np.zeros(op.get_ndof())
     sampler.fix_rhs(sampler.operator_apply(0, mean_x_exact))
     sampler.set_state(np.zeros(op.get_ndof()))
     sampler.sample(sampling_params.nwarmup)
-    sampler.field_stats(1)
+    sampler.field_stats(1, batch=stderr_batch)
+    fields = {"mean_exact": mean_x_exact}
     try:
         sampler.sample(sampling_params.nsamples)
-        mean, variance = sampler.field_mean_variance()
+        fields["mean"], fields["variance"] = mean, variance = sampler.field_mean_variance()
+        if stderr_batch is not None:
+            fields["mean_stderr"] = sampler.field_mean_stderr()[1]
+            fields["iact"] = sampler.field_iact()
     finally:
         sampler.field_stats_off()
-    write_vtk("posterior.vtk", op.get_lattice(), {"mean": mean, "variance": variance, "mean_exact": mean_x_exact})
+    write_vtk("posterior.vtk", op.get_lattice(), fields)
     if measurement_params.dim == 2:
         write_vtk_circle(measurement_params.sample_location, measurement_params.radius, "sample_location.vtk")
     return mean, variance, mean_x_exact
@@ -236,11 +242,15 @@ def posterior_statistics(sampler, exact: ExactTargets, sampling_params: Sampling
 def main(argv=None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
     batch = 1
-    if len(argv) == 3 and argv[0] == "--convergence-batch":  # concurrent measure_convergence chains
-        batch = int(argv[1])
+    stderr_batch = None
+    while len(argv) >= 3 and argv[0] in ("--convergence-batch", "--stderr-batch"):
+        if argv[0] == "--convergence-batch":  # concurrent measure_convergence chains
+            batch = int(argv[1])
+        else:  # posterior_statistics: batch means of this many cycles (mean_stderr and iact in posterior.vtk)
+            stderr_batch = int(argv[1])
         argv = argv[2:]
     if len(argv) != 1:
-        print(f"Usage: {sys.argv[0]} [--convergence-batch N] CONFIGURATIONFILE")
+        print(f"Usage: {sys.argv[0]} [--convergence-batch N] [--stderr-batch B] CONFIGURATIONFILE")
         return -1
     t_start = time.time()
     print("\n+--------------------------------+")
@@ -317,8 +327,9 @@ def main(argv=None) -> int:
         measure_convergence(sampler, exact, sampling_params, measurement_params, "convergence_multigridmc.txt",
                             batch)
         if general.save_posterior_statistics:
-            posterior_statistics(sampler, exact, sampling_params, measurement_params)
-            print("  posterior_statistics: mean, variance and mean_exact written to posterior.vtk")
+            posterior_statistics(sampler, exact, sampling_params, measurement_params, stderr_batch)
+            print("  posterior_statistics: mean, variance and mean_exact written to posterior.vtk"
+                  + ("" if stderr_batch is None else f"; mean_stderr and iact from batches of {stderr_batch} cycles"))
         print()
     secs = int(time.time() - t_start)
     print(f"Completed run at {datetime.datetime.now().ctime()}")

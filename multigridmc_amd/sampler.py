@@ -369,6 +369,21 @@ def describe(config: MgmcConfig) -> list:
     return levels
 
 
+def batch_means_estimates(states_per_batch, nb, bm2, n, m2):
+    """(stderr, iact) of the batch-means estimator, per vertex: nb completed batches of states_per_batch
+    = B K states each, bm2 the sum of squared deviations of their means, m2 that of the n recorded states.
+        stderr = sqrt(bm2 / (nb - 1) / nb)                    the standard error of the mean of nb batches
+        iact   = B K (bm2 / (nb - 1)) / (m2 / (n - 1))        the variance of a batch mean is var tau / (B K)
+    A vertex whose m2 is 0 has iact nan.  ValueError while nb < 2."""
+    if nb < 2:
+        raise ValueError("batch means: fewer than two completed batches")
+    bm2, m2 = np.asarray(bm2, dtype=np.float64), np.asarray(m2, dtype=np.float64)
+    bvar = bm2 / (nb - 1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        iact = states_per_batch * bvar / (m2 / (n - 1))
+    return np.sqrt(bvar / nb), iact
+
+
 class MultigridMCSampler:
     """Device MGMC sampler with the reference's Sampler interface (sampler/sampler.hh:23-72).
 
@@ -589,12 +604,17 @@ class MultigridMCSampler:
         self._chk(self.lib.mgmc_reset_moments(self.handle))
 
     # -- pointwise field statistics on the device (posterior_statistics, driver_mgmc.cc:118-171) --
-    def field_stats(self, stride: int = 1):
+    def field_stats(self, stride: int = 1, batch=None):
         """From now on every stride-th cycle (numbered 1, 2, ... from this call), whichever call runs it,
         folds the state of every chain into one running mean field and one M2 field in HBM
         (mgmc_field_stats_enable; the Welford update of qoi_moments, chains in order).  On a sampler
-        that already records: a reset with the new stride."""
-        self._chk(self.lib.mgmc_field_stats_enable(self.handle, int(stride)))
+        that already records: a reset with the new stride.
+        batch=B: also the batch means of B recorded cycles each, pooled over the chains
+        (mgmc_field_stats_enable_batched), for field_mean_stderr and field_iact."""
+        if batch is None:
+            self._chk(self.lib.mgmc_field_stats_enable(self.handle, int(stride)))
+        else:
+            self._chk(self.lib.mgmc_field_stats_enable_batched(self.handle, int(stride), int(batch)))
 
     def field_stats_off(self):
         """Free the fields; the cycle is again the one of a sampler that never recorded them."""
@@ -625,6 +645,37 @@ class MultigridMCSampler:
         if n == 0:
             raise ValueError("no state has been recorded yet")
         return mean, m2 / n
+
+    def field_batch_info(self) -> dict:
+        """{"batch": batch length in recorded cycles (0 without batching or while disabled),
+        "nbatches": completed batches}"""
+        b, nb = ctypes.c_int(), ctypes.c_uint64()
+        self._chk(self.lib.mgmc_field_stats_batch_info(self.handle, ctypes.byref(b), ctypes.byref(nb)))
+        return {"batch": b.value, "nbatches": nb.value}
+
+    def field_batch_moments(self):
+        """(nb, bmean, bM2): the completed batches, and the mean and the sum of squared deviations of
+        their means per vertex (reference layout); a partial batch is in neither."""
+        bmean, bm2 = np.empty(self.ndof), np.empty(self.ndof)
+        self._chk(self.lib.mgmc_field_stats_get_batch(self.handle, _dp(bmean), _dp(bm2), self.ndof))
+        return self.field_batch_info()["nbatches"], bmean, bm2
+
+    def _batch_means(self):
+        info = self.field_batch_info()
+        n, mean, m2 = self.field_moments()
+        nb, _, bm2 = self.field_batch_moments()
+        return batch_means_estimates(info["batch"] * self.nchains, nb, bm2, n, m2), mean
+
+    def field_mean_stderr(self):
+        """(mean, stderr): the sample mean per vertex and its Monte Carlo standard error from the batch
+        means, sqrt(bM2 / (nb - 1) / nb).  ValueError with fewer than two completed batches."""
+        (stderr, _), mean = self._batch_means()
+        return mean, stderr
+
+    def field_iact(self):
+        """The integrated autocorrelation time per vertex from the batch means,
+        B K (bM2 / (nb - 1)) / (M2 / (n - 1)).  ValueError with fewer than two completed batches."""
+        return self._batch_means()[0][1]
 
     def get_series(self, n: int, chain: int = 0) -> np.ndarray:
         """The QoI series of the last sample / sample_async call (waits for this handle's stream)."""
@@ -875,4 +926,5 @@ __all__ = [
     "Lattice", "Lattice2d", "Lattice3d", "ShiftedLaplaceFDOperator", "MultigridMCSampler",
     "HipMulticolourSORSmoother", "SORSmoother", "SSORSmoother", "SORSmootherFactory", "SSORSmootherFactory", "measurement_vector_index", "ConstantCorrelationLengthModel",
     "PeriodicCorrelationLengthModel", "SquaredShiftedLaplaceFDOperator", "comm_unique_id", "make_config", "describe", "FORWARD", "BACKWARD",
+    "batch_means_estimates",
 ]
