@@ -369,6 +369,42 @@ int mgmc_field_stats_get_batch(mgmc_handle* h, double* bmean, double* bm2, size_
                                                           /* reference layout, n = ndof; either pointer may be NULL;
                                                              waits for the handle's stream */
 
+/* ---- whole-field energy: x^T Q x and f^T x of the level-0 state, reduced on the device ----
+ * Per chain two doubles:
+ *     xqx = x^T A x + sum_k (B_k^T x)^2 / Sigma_k   (the second term once mgmc_set_lowrank ran),
+ *     fx  = f^T x, f the vector of mgmc_set_rhs (never a low-rank-patched copy); +0.0 while f is all +0.0.
+ * At stationarity E = xqx - 2 fx + f^T Q^{-1} f is chi-square with ndof degrees of freedom (mean ndof,
+ * variance 2 ndof), and -xqx / 2 + fx is the Gaussian log-density of the state up to a constant.  The sums run
+ * in a fixed order (no atomics): a chain's values do not depend on scheduling, on the
+ * other chains of its batch or on MGMC_GRAPH_UNROLL.
+ * mgmc_energy evaluates the current device state, nchains values each; nothing is recorded and the state is
+ * untouched.  flags: MGMC_ENERGY_GENERAL takes the general kernel where the level would take the z-marching
+ * one (the two agree to rounding, not bitwise). */
+#define MGMC_ENERGY_GENERAL 1u
+int mgmc_energy(mgmc_handle* h, unsigned flags, double* xqx, double* fx);
+/* Recording: while enabled, every stride-th cycle of the handle (numbered 1, 2, ... from the enable / reset on,
+ * whichever call ran it) appends (xqx, fx) of every chain to a series that keeps the first `capacity` records,
+ * and folds E = xqx - 2 fx into per-chain Welford moments (the update of mgmc_qoi_moments), which keep counting
+ * past the capacity.  The op sits after the QoI record and before the field statistics, in the timed cycle's
+ * last segment; on a cycle that is not recorded its kernels leave at once.  mgmc_set_state, mgmc_set_rhs and
+ * mgmc_set_sample_index do not reset the record; mgmc_set_lowrank and mgmc_set_qoi_vector keep it going.
+ * Disabled (the default) the cycle and its graphs are those of a handle that never enabled it.
+ * MGMC_E_INVALID: a NULL handle or pointer, stride < 1, capacity < 1, a chain out of range, get_series / moments
+ * / reset while disabled, n beyond the records kept; MGMC_E_NOMEM: the buffers could not be allocated (the
+ * handle stays as it was). */
+int mgmc_energy_record_enable(mgmc_handle* h, int stride, int64_t capacity);
+                                                          /* allocates + zeroes, rebuilds graphs; on an enabled
+                                                             handle: a reset with the new stride (and capacity) */
+int mgmc_energy_record_disable(mgmc_handle* h);           /* frees, rebuilds graphs; no-op when disabled */
+int mgmc_energy_record_reset(mgmc_handle* h);             /* zero moments and both counters; no graph rebuild */
+int mgmc_energy_record_info(const mgmc_handle* h, int* enabled, int* stride, uint64_t* ncycles, uint64_t* nrecorded);
+                                                          /* cycles seen and cycles recorded since enable / reset */
+int mgmc_energy_get_series(mgmc_handle* h, int chain, double* xqx, double* fx, size_t n);
+                                                          /* the first n records, n <= min(nrecorded, capacity);
+                                                             either pointer may be NULL; waits for the stream */
+int mgmc_energy_moments(mgmc_handle* h, int chain, double out[3]);
+                                                          /* (n, mean, M2) of E = xqx - 2 fx */
+
 /* ---- component entry points (host buffers, reference layout) used by the parity tests ---- */
 /* y = Q_level x  (LinearOperator::apply; Q = A + B Sigma^{-1} B^T once mgmc_set_lowrank ran) */
 int mgmc_operator_apply(mgmc_handle* h, int level, const double* x, double* y);

@@ -186,6 +186,32 @@ class HipMultigridMCSampler {
     void field_moments(double* mean, double* m2) const {
         check(mgmc_field_stats_get(h_.get(), mean, m2, ndof_), h_.get(), "mgmc_field_stats_get");
     }
+    // Whole-field energy, reduced on the device (mgmc_energy*): xqx = x^T A x + sum_k (B_k^T x)^2 / Sigma_k and
+    // fx = f^T x of the current state, nchains() values each; general: the general kernel on a z-sweep level
+    void energy(double* xqx, double* fx, bool general = false) const {
+        check(mgmc_energy(h_.get(), general ? MGMC_ENERGY_GENERAL : 0u, xqx, fx), h_.get(), "mgmc_energy");
+    }
+    // every stride-th cycle from here on records (xqx, fx) per chain: a series of the first `capacity` records
+    // and Welford moments of E = xqx - 2 fx
+    void energy_record(int stride = 1, int64_t capacity = 4096) {
+        check(mgmc_energy_record_enable(h_.get(), stride, capacity), h_.get(), "mgmc_energy_record_enable");
+    }
+    void energy_record_off() { check(mgmc_energy_record_disable(h_.get()), h_.get(), "mgmc_energy_record_disable"); }
+    void reset_energy_record() { check(mgmc_energy_record_reset(h_.get()), h_.get(), "mgmc_energy_record_reset"); }
+    // cycles recorded since the enable / reset; 0 while disabled
+    uint64_t energy_recorded() const {
+        uint64_t n = 0;
+        check(mgmc_energy_record_info(h_.get(), nullptr, nullptr, nullptr, &n), h_.get(), "mgmc_energy_record_info");
+        return n;
+    }
+    // the first n records of one chain (either pointer may be nullptr)
+    void energy_series(int chain, double* xqx, double* fx, size_t n) const {
+        check(mgmc_energy_get_series(h_.get(), chain, xqx, fx, n), h_.get(), "mgmc_energy_get_series");
+    }
+    // (n, mean, M2) of E = xqx - 2 fx of one chain
+    void energy_moments(int chain, double out[3]) const {
+        check(mgmc_energy_moments(h_.get(), chain, out), h_.get(), "mgmc_energy_moments");
+    }
 
    private:
     void adopt(mgmc_handle* h) {

@@ -130,6 +130,13 @@ SIGNATURES = [
     ("mgmc_field_stats_enable_batched", c_int, [_H, c_int, c_int]),
     ("mgmc_field_stats_batch_info", c_int, [_H, POINTER(c_int), POINTER(c_uint64)]),
     ("mgmc_field_stats_get_batch", c_int, [_H, _DP, _DP, c_size_t]),
+    ("mgmc_energy", c_int, [_H, ctypes.c_uint, _DP, _DP]),
+    ("mgmc_energy_record_enable", c_int, [_H, c_int, c_int64]),
+    ("mgmc_energy_record_disable", c_int, [_H]),
+    ("mgmc_energy_record_reset", c_int, [_H]),
+    ("mgmc_energy_record_info", c_int, [_H, POINTER(c_int), POINTER(c_int), POINTER(c_uint64), POINTER(c_uint64)]),
+    ("mgmc_energy_get_series", c_int, [_H, c_int, _DP, _DP, c_size_t]),
+    ("mgmc_energy_moments", c_int, [_H, c_int, _DP]),
     ("mgmc_operator_apply", c_int, [_H, c_int, _DP, _DP]),
     ("mgmc_smoother_apply", c_int, [_H, c_int, c_int, c_int, _DP, _DP]),
     ("mgmc_sor_smoother_apply", c_int, [_H, c_int, c_int, c_int, _DP, _DP]),

@@ -1765,10 +1765,114 @@ int build_tails(mgmc_handle* h) {
 // The field-statistics op is the last op of the cycle, after OP_QOI, while the statistics are enabled and
 // absent otherwise: appended once the passes above have run (none of them sees it), so the rest of the
 // op list is what it is without the statistics.  It lies behind seg_end_post: in the timed graph's last
-// (QoI) segment.
+// (QoI) segment.  The energy op (mgmc_energy_record_enable) likewise, between OP_QOI and OP_FIELDSTATS.
 void sync_fieldstats_op(mgmc_handle* h) {
-    while (!h->ops.empty() && h->ops.back().kind == OP_FIELDSTATS) h->ops.pop_back();
+    while (!h->ops.empty() && (h->ops.back().kind == OP_FIELDSTATS || h->ops.back().kind == OP_ENERGY)) h->ops.pop_back();
+    if (h->en_ctl && !h->ops.empty()) h->ops.push_back({OP_ENERGY, 0, 0, 0, 0});
     if (h->fs_mean && !h->ops.empty()) h->ops.push_back({OP_FIELDSTATS, 0, 0, 0, 0});
+}
+
+// ---- whole-field energy (mgmc_energy.hpp): the reduction launches of level 0's canonical buffer ----
+// partial slots per chain of the kernel plan_energy picks, and of the general kernel (mgmc_energy's flag)
+static long long energy_slots(const Level& lv, bool general) {
+    return plan_energy(lv.shape, lv.paths, general).zmarch ? energy_z_slots(lv.L) : energy_g_slots(lv.L);
+}
+
+// the scratch of the reductions, sized for either kernel; MGMC_E_NOMEM leaves the handle as it was
+static int energy_scratch(mgmc_handle* h) {
+    if (h->en_part) return MGMC_OK;
+    const Level& lv = h->levels[0];
+    const size_t slots = (size_t)std::max(energy_slots(lv, false), energy_slots(lv, true));
+    const size_t blocks = (slots + EN_RBLK - 1) / EN_RBLK;
+    double2 *a = nullptr, *b = nullptr, *c = nullptr;
+    if (hipMalloc(&a, slots * h->nchains * sizeof(double2)) != hipSuccess ||
+        hipMalloc(&b, blocks * h->nchains * sizeof(double2)) != hipSuccess ||
+        hipMalloc(&c, h->nchains * sizeof(double2)) != hipSuccess) {
+        (void)hipGetLastError();
+        if (a) hipFree(a);
+        if (b) hipFree(b);
+        if (c) hipFree(c);
+        return fail(h, MGMC_E_NOMEM, "device allocation failed (energy reduction)");
+    }
+    h->en_part = a, h->en_part2 = b, h->en_out = c;
+    poison_fill(h, a, slots * h->nchains * sizeof(double2));
+    poison_fill(h, b, blocks * h->nchains * sizeof(double2));
+    poison_fill(h, c, h->nchains * sizeof(double2));
+    return MGMC_OK;
+}
+
+// (xqx, fx) of every chain's level-0 state into en_out; ctl (recording, the cycle's op): only on a recorded
+// cycle, then also the series, the moments and the counters (k_energy_record).  f is level 0's own buffer: at
+// the end of a cycle it holds the user's values on every low-rank path (the row-list, small and in-place paths
+// restore it after their last sweep, the dense-column path patches copies), and while f0_zero holds it is not read.
+static void launch_energy(mgmc_handle* h, bool general, uint64_t* ctl, hipStream_t s) {
+    const Level& lv = h->levels[0];
+    const int nch = h->nchains, dim = lv.spec.dim, np = lv.spec.npoints;
+    const EnergyPlan plan = plan_energy(lv.shape, lv.paths, general);
+    const bool fz = h->f0_zero;
+    const long long cs = lv.L.nstore;
+    long long nslot;
+    lds_poison(h, lv, s);
+    if (plan.zmarch) {
+        EnergyZArgs a;
+        a.L = lv.L;
+        a.x = lv.x;
+        a.f = lv.f;
+        a.dg = lv.vd[0];
+        a.ac = lv.S.a[13], a.ax = lv.S.a[14], a.ay = lv.S.a[16], a.az = lv.S.a[22];
+        a.cs = cs;
+        a.part = h->en_part;
+        a.nchunk = energy_z_chunks(lv.L);
+        a.ctl = ctl;
+        nslot = energy_z_slots(lv.L);
+        const dim3 grid((lv.L.nx / 2) / EN_XP, (lv.L.ny - 1 + EN_TY - 1) / EN_TY, a.nchunk * nch);
+        if (plan.vardiag && fz) hipLaunchKernelGGL((k_energy_z<true, true>), grid, dim3(EN_NT), 0, s, a);
+        else if (plan.vardiag) hipLaunchKernelGGL((k_energy_z<false, true>), grid, dim3(EN_NT), 0, s, a);
+        else if (fz) hipLaunchKernelGGL((k_energy_z<true, false>), grid, dim3(EN_NT), 0, s, a);
+        else hipLaunchKernelGGL((k_energy_z<false, false>), grid, dim3(EN_NT), 0, s, a);
+    } else {
+        const int nzb = energy_g_zblocks(lv.L);
+        nslot = energy_g_slots(lv.L);
+        const dim3 block(EN_GX, EN_GY, 1);
+        const dim3 grid((lv.L.nx - 1 + EN_GX - 1) / EN_GX, (lv.L.ny - 1 + EN_GY - 1) / EN_GY, nzb * nch);
+        const uint64_t* cc = ctl;
+#define EN_LAUNCH_GENERAL(D, P)                                                                                \
+    do {                                                                                                         \
+        if (fz) hipLaunchKernelGGL((k_energy_general<D, P, true>), grid, block, 0, s, lv.L, (const double*)lv.x, \
+                                   (const double*)lv.f, lv.S, cs, h->en_part, nzb, cc);                          \
+        else hipLaunchKernelGGL((k_energy_general<D, P, false>), grid, block, 0, s, lv.L, (const double*)lv.x,   \
+                                (const double*)lv.f, lv.S, cs, h->en_part, nzb, cc);                             \
+    } while (0)
+#define EN_LAUNCH_FIELD(D)                                                                                    \
+    do {                                                                                                        \
+        if (fz) hipLaunchKernelGGL((k_energy_field<D, true>), grid, block, 0, s, lv.L, (const double*)lv.x,     \
+                                   (const double*)lv.f, lv.F, cs, h->en_part, nzb, cc);                         \
+        else hipLaunchKernelGGL((k_energy_field<D, false>), grid, block, 0, s, lv.L, (const double*)lv.x,       \
+                                (const double*)lv.f, lv.F, cs, h->en_part, nzb, cc);                            \
+    } while (0)
+        if (plan.field && dim == 3) EN_LAUNCH_FIELD(3);
+        else if (plan.field) EN_LAUNCH_FIELD(2);
+        else if (dim == 3 && np == 7) EN_LAUNCH_GENERAL(3, 7);
+        else if (dim == 3) EN_LAUNCH_GENERAL(3, 27);
+        else if (np == 5) EN_LAUNCH_GENERAL(2, 5);
+        else EN_LAUNCH_GENERAL(2, 9);
+#undef EN_LAUNCH_GENERAL
+#undef EN_LAUNCH_FIELD
+    }
+    const double2* part = h->en_part;
+    if (nslot > EN_RBLK) {  // a fixed-order second stage: blocks of EN_RBLK partials
+        const int nblk = (int)((nslot + EN_RBLK - 1) / EN_RBLK);
+        hipLaunchKernelGGL(k_energy_reduce, dim3(nblk, nch), dim3(64), 0, s, (const double2*)h->en_part, nslot,
+                           h->en_part2, nblk, (const uint64_t*)ctl);
+        part = h->en_part2;
+        nslot = nblk;
+    }
+    if (lv.lr.m > 0) {  // w = B^T x (lr.w and the dots' partials are live only within an op)
+        lds_poison(h, lv, s);
+        lr_dots(lv, lv.x, LR_SCALE_ONE, s, nch);
+    }
+    hipLaunchKernelGGL(k_energy_record, dim3(1), dim3(64 * nch), 0, s, part, nslot, nch, (const double*)lv.lr.w,
+                       (const double*)lv.lr.sc_inv, lv.lr.m, h->en_out, ctl, h->en_sq, h->en_sf, h->en_mom);
 }
 
 void enqueue_ops(mgmc_handle* h, size_t begin, size_t end, hipStream_t s) {
@@ -1908,6 +2012,10 @@ void enqueue_ops(mgmc_handle* h, size_t begin, size_t end, hipStream_t s) {
                 hipLaunchKernelGGL(k_qoi_record, dim3(1), dim3(64 * ((nch + 63) / 64)), 0, s,
                                    (const double*)h->levels[0].x, h->ctrl, h->series, h->series_cap, h->mom, nch,
                                    (long long)h->levels[0].L.nstore);
+                break;
+            }
+            case OP_ENERGY: {  // (level 0's canonical buffer, as below)
+                launch_energy(h, false, h->en_ctl, s);
                 break;
             }
             case OP_FIELDSTATS: {  // level 0's canonical buffer holds the cycle's state (OP_COPY before OP_QOI)
@@ -2399,6 +2507,7 @@ static int create_impl(const mgmc_config* cfg, const CsrHost* csr, int device, u
         const LevelShape sh{cfg->dim, lv.spec.npoints, lv.L.nx, lv.L.ny, lv.L.nz, lv.field,
                             st[4] == st[22] && st[10] == st[16] && st[12] == st[14], lv.fold, has_coarser,
                             l == 0 && fine_vardiag};
+        lv.shape = sh;
         lv.sweep = plan_sweep(sh, h->paths, (int)l, tail0);
         if (has_coarser) lv.res = plan_residual(sh, h->paths, specs[l + 1].n[0], specs[l + 1].n[1], specs[l + 1].n[2]);
         if (lv.vardiag()) {  // the VD kernels' per-vertex streams, from the coefficient field (which stays)
@@ -2690,6 +2799,13 @@ int mgmc_destroy(mgmc_handle* h) {
     if (h->fs_bsum) hipFree(h->fs_bsum);
     if (h->fs_bmean) hipFree(h->fs_bmean);
     if (h->fs_bm2) hipFree(h->fs_bm2);
+    if (h->en_part) hipFree(h->en_part);
+    if (h->en_part2) hipFree(h->en_part2);
+    if (h->en_out) hipFree(h->en_out);
+    if (h->en_ctl) hipFree(h->en_ctl);
+    if (h->en_sq) hipFree(h->en_sq);
+    if (h->en_sf) hipFree(h->en_sf);
+    if (h->en_mom) hipFree(h->en_mom);
     if (h->stream) hipStreamDestroy(h->stream);
     delete h;
     return MGMC_OK;
@@ -2822,7 +2938,8 @@ int mgmc_set_rhs(mgmc_handle* h, const double* f, size_t n) {
     const bool zero = rhs_bits_all_zero(bits);
     if (zero != h->f0_zero) {
         h->f0_zero = zero;
-        if (mark_rhs_zero(h)) return build_graphs(h);
+        // (a recording energy op reads f0_zero too: its FZ instances, mgmc_energy.hpp)
+        if (mark_rhs_zero(h) || h->en_ctl) return build_graphs(h);
     }
     return MGMC_OK;
 }
@@ -3565,6 +3682,159 @@ int mgmc_field_stats_get_batch(mgmc_handle* h, double* bmean, double* bm2, size_
     int rc = MGMC_OK;
     if (bmean && (rc = download(h, 0, h->fs_bmean, bmean))) return rc;
     if (bm2 && (rc = download(h, 0, h->fs_bm2, bm2))) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MGMC_OK;
+}
+
+// ---------------- whole-field energy x^T Q x, f^T x (mgmc_energy.hpp) ----------------
+
+int mgmc_energy(mgmc_handle* h, unsigned flags, double* xqx, double* fx) {
+    if (!h) return fail(nullptr, MGMC_E_INVALID, "null handle");
+    if (!xqx || !fx) return fail(h, MGMC_E_INVALID, "null argument");
+    if (flags & ~(unsigned)MGMC_ENERGY_GENERAL) return fail(h, MGMC_E_INVALID, "energy: unknown flag");
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = energy_scratch(h);
+    if (rc) return rc;
+    launch_energy(h, (flags & MGMC_ENERGY_GENERAL) != 0, nullptr, h->stream);
+    HIPCHK(h, hipGetLastError());
+    std::vector<double2> out(h->nchains);
+    HIPCHK(h, hipMemcpyAsync(out.data(), h->en_out, out.size() * sizeof(double2), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (int c = 0; c < h->nchains; ++c) {
+        xqx[c] = out[c].x;
+        fx[c] = out[c].y;
+    }
+    return MGMC_OK;
+}
+
+// zero the moments and the counters, set the stride (the capacity stays); on the handle's stream
+static int energy_zero(mgmc_handle* h, int stride) {
+    const uint64_t ctl0[EN_CTL_WORDS] = {0, 0, (uint64_t)stride, h->en_cap};
+    HIPCHK(h, hipMemsetAsync(h->en_mom, 0, 4 * (size_t)h->nchains * sizeof(double), h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->en_ctl, ctl0, sizeof(ctl0), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));  // (ctl0 is on this stack)
+    h->en_stride = stride;
+    return MGMC_OK;
+}
+
+static void energy_free_record(mgmc_handle* h) {
+    if (h->en_ctl) hipFree(h->en_ctl);
+    if (h->en_sq) hipFree(h->en_sq);
+    if (h->en_sf) hipFree(h->en_sf);
+    if (h->en_mom) hipFree(h->en_mom);
+    h->en_ctl = nullptr;
+    h->en_sq = h->en_sf = h->en_mom = nullptr;
+    h->en_stride = 0;
+    h->en_cap = 0;
+}
+
+int mgmc_energy_record_enable(mgmc_handle* h, int stride, int64_t capacity) {
+    if (!h) return fail(nullptr, MGMC_E_INVALID, "null handle");
+    if (stride < 1) return fail(h, MGMC_E_INVALID, "energy record: stride must be >= 1");
+    if (capacity < 1) return fail(h, MGMC_E_INVALID, "energy record: capacity must be >= 1");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (h->en_ctl && (uint64_t)capacity == h->en_cap) return energy_zero(h, stride);  // a reset (same graphs)
+    // disabled, or another capacity: the handle takes the new buffers only once all are there
+    int rc = energy_scratch(h);
+    if (rc) return rc;
+    const size_t sbytes = (size_t)capacity * h->nchains * sizeof(double);
+    uint64_t* ctl = nullptr;
+    double *sq = nullptr, *sf = nullptr, *mom = nullptr;
+    if (hipMalloc(&ctl, EN_CTL_WORDS * sizeof(uint64_t)) != hipSuccess || hipMalloc(&sq, sbytes) != hipSuccess ||
+        hipMalloc(&sf, sbytes) != hipSuccess || hipMalloc(&mom, 4 * (size_t)h->nchains * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        if (ctl) hipFree(ctl);
+        if (sq) hipFree(sq);
+        if (sf) hipFree(sf);
+        if (mom) hipFree(mom);
+        return fail(h, MGMC_E_NOMEM, "device allocation failed (energy record)");
+    }
+    destroy_graphs(h);  // (an enabled handle's hold the old buffers' addresses)
+    energy_free_record(h);
+    h->en_ctl = ctl, h->en_sq = sq, h->en_sf = sf, h->en_mom = mom;
+    h->en_cap = (uint64_t)capacity;
+    poison_fill(h, sq, sbytes);
+    poison_fill(h, sf, sbytes);
+    rc = energy_zero(h, stride);
+    if (rc == MGMC_OK) {
+        sync_fieldstats_op(h);
+        rc = build_graphs(h);
+    }
+    if (rc != MGMC_OK) {  // back to the cycle without the op
+        const std::string err = h->last_error;
+        destroy_graphs(h);
+        energy_free_record(h);
+        sync_fieldstats_op(h);
+        (void)build_graphs(h);
+        return fail(h, rc, err);
+    }
+    return MGMC_OK;
+}
+
+int mgmc_energy_record_disable(mgmc_handle* h) {
+    if (!h) return fail(nullptr, MGMC_E_INVALID, "null handle");
+    if (!h->en_ctl) return MGMC_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    destroy_graphs(h);  // they hold the buffers' addresses
+    energy_free_record(h);
+    sync_fieldstats_op(h);
+    return build_graphs(h);
+}
+
+int mgmc_energy_record_reset(mgmc_handle* h) {
+    if (!h) return fail(nullptr, MGMC_E_INVALID, "null handle");
+    if (!h->en_ctl) return fail(h, MGMC_E_INVALID, "the energy record is not enabled (mgmc_energy_record_enable)");
+    HIPCHK(h, hipSetDevice(h->device));
+    return energy_zero(h, h->en_stride);
+}
+
+// ctl[0], ctl[1] of an enabled handle (waits for the handle's stream)
+static int energy_counters(const mgmc_handle* h, uint64_t out[2]) {
+    if (hipSetDevice(h->device) != hipSuccess ||
+        hipMemcpyAsync(out, h->en_ctl, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+        hipStreamSynchronize(h->stream) != hipSuccess)
+        return fail(nullptr, MGMC_E_HIP, "energy record: reading the counters failed");
+    return MGMC_OK;
+}
+
+int mgmc_energy_record_info(const mgmc_handle* h, int* enabled, int* stride, uint64_t* ncycles, uint64_t* nrecorded) {
+    if (!h) return fail(nullptr, MGMC_E_INVALID, "null handle");
+    if (enabled) *enabled = h->en_ctl ? 1 : 0;
+    if (stride) *stride = h->en_stride;
+    uint64_t cnt[2] = {0, 0};
+    if (h->en_ctl && (ncycles || nrecorded)) {
+        int rc = energy_counters(h, cnt);
+        if (rc) return rc;
+    }
+    if (ncycles) *ncycles = cnt[0];
+    if (nrecorded) *nrecorded = cnt[1];
+    return MGMC_OK;
+}
+
+int mgmc_energy_get_series(mgmc_handle* h, int chain, double* xqx, double* fx, size_t n) {
+    if (!h) return fail(nullptr, MGMC_E_INVALID, "null handle");
+    if (!h->en_ctl) return fail(h, MGMC_E_INVALID, "the energy record is not enabled (mgmc_energy_record_enable)");
+    if (chain < 0 || chain >= h->nchains) return fail(h, MGMC_E_INVALID, "chain index out of range");
+    uint64_t cnt[2];
+    int rc = energy_counters(h, cnt);
+    if (rc) return rc;
+    if (n > std::min(cnt[1], h->en_cap)) return fail(h, MGMC_E_INVALID, "energy series: more values asked for than kept");
+    const size_t o = (size_t)chain * h->en_cap;
+    if (xqx && n) HIPCHK(h, hipMemcpyAsync(xqx, h->en_sq + o, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (fx && n) HIPCHK(h, hipMemcpyAsync(fx, h->en_sf + o, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MGMC_OK;
+}
+
+int mgmc_energy_moments(mgmc_handle* h, int chain, double out[3]) {
+    if (!h) return fail(nullptr, MGMC_E_INVALID, "null handle");
+    if (!out) return fail(h, MGMC_E_INVALID, "null argument");
+    if (!h->en_ctl) return fail(h, MGMC_E_INVALID, "the energy record is not enabled (mgmc_energy_record_enable)");
+    if (chain < 0 || chain >= h->nchains) return fail(h, MGMC_E_INVALID, "chain index out of range");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipMemcpyAsync(out, h->en_mom + 4 * chain, 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return MGMC_OK;
 }

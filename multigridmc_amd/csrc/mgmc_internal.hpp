@@ -48,6 +48,7 @@ static_assert(MGMC_LAYOUT_POINT == mgmc::LF_POINT && MGMC_LAYOUT_PAIRS == mgmc::
 #include "mgmc_level_plan.hpp"
 #include "mgmc_rhs_zero.hpp"
 #include "mgmc_fieldstats.hpp"
+#include "mgmc_energy.hpp"
 
 using namespace mgmc;
 
@@ -66,8 +67,10 @@ enum OpKind {
     OP_COARSE_CHOL = 6,
     OP_TAIL = 7,     // the sub-cycle of the coarsest levels in one workgroup (mgmc_tail.hpp)
     OP_SWEEP_RESTRICT = 8,  // 2D Galerkin level: last pre-sweep + residual + restriction (mgmc_qrestrict.hpp)
-    OP_FIELDSTATS = 9       // pointwise mean / M2 of the level-0 state (mgmc_fieldstats.hpp); the last op, only
+    OP_FIELDSTATS = 9,      // pointwise mean / M2 of the level-0 state (mgmc_fieldstats.hpp); the last op, only
                             // while mgmc_field_stats_enable holds
+    OP_ENERGY = 10          // x^T Q x and f^T x of the level-0 state (mgmc_energy.hpp); after OP_QOI and before
+                            // OP_FIELDSTATS, only while mgmc_energy_record_enable holds
 };
 
 struct Op {
@@ -178,6 +181,7 @@ struct Level {
     size_t lds_bytes = 0;  // >0 if the whole-level LDS kernel can hold x and f
     int num_cu = 256;      // compute units of the handle's device (grid sizing; MI355X: 256)
     uint32_t paths = 0;    // PathFlag bits of the handle (MGMC_DISABLE)
+    LevelShape shape{};    // what the level's plan was made from (plan_energy reads it again for level 0)
     SweepKernel sweep = SweepKernel::COLOUR;  // the level's noisy sweep (mgmc_level_plan.hpp plan_sweep)
     ResidualPlan res;      // its residual + restriction onto the next level (plan_residual)
     bool field = false;    // per-vertex coefficients (mgmc_create_csr, mgmc_field.hpp)
@@ -260,6 +264,18 @@ struct mgmc_handle {
     double* fs_bmean = nullptr;     // Welford mean and M2 of the completed batches' means
     double* fs_bm2 = nullptr;
     int fs_batch = 0;               // batch length in recorded cycles (0: no batching)
+    // whole-field energy (mgmc_energy*, mgmc_energy.hpp).  The reduction scratch is allocated by the first call
+    // that needs it and kept: workgroup partials, their block sums, the chains' (xqx, fx)
+    double2* en_part = nullptr;
+    double2* en_part2 = nullptr;
+    double2* en_out = nullptr;
+    // ... recording (mgmc_energy_record_*): enabled <=> en_ctl != nullptr
+    uint64_t* en_ctl = nullptr;     // [0] cycles seen [1] records [2] stride [3] capacity
+    double* en_sq = nullptr;        // the series of xqx and of fx, capacity values per chain
+    double* en_sf = nullptr;
+    double* en_mom = nullptr;       // (n, mean, M2, pad) of E = xqx - 2 fx per chain
+    int en_stride = 0;
+    uint64_t en_cap = 0;
     std::string last_error;
     ncclComm_t comm = nullptr;
     int nranks = 1, rank = 0;

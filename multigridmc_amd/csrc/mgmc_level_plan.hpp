@@ -288,6 +288,24 @@ inline ResidualPlan plan_residual(const LevelShape& sh, uint32_t paths, int cnx,
     return p;
 }
 
+// ---- the whole-field energy x^T Q x, f^T x of level 0 (mgmc_energy.hpp) ----
+struct EnergyPlan {
+    bool zmarch = false;   // k_energy_z: the forward-neighbour z-march of a symmetric 7-point level
+    bool vardiag = false;  // ... its VD instance (the diagonal streamed per vertex)
+    bool field = false;    // the general kernel of a per-vertex-coefficient level (k_energy_field); neither:
+                           // k_energy_general<dim, npoints>
+};
+// The z-march goes wherever level 0 runs the z-sweep (plan_sweep's conditions: symmetric 7-point stencil, rows of
+// whole 64-vertex tiles, MGMC_DISABLE=zsweep leaves it to the general kernels); force_general: mgmc_energy's
+// flag, the general kernel on a z-sweep level (how the two are compared).
+inline EnergyPlan plan_energy(const LevelShape& sh, uint32_t paths, bool force_general) {
+    EnergyPlan p;
+    p.zmarch = !force_general && plan_sweep(sh, paths, 0, -1) == SweepKernel::ZSWEEP;
+    p.vardiag = p.zmarch && sh.field;
+    p.field = !p.zmarch && sh.field;
+    return p;
+}
+
 // ---- the coarsest levels' sub-cycle in one workgroup (k_tail) ----
 // (tail_start below; without a run_ops argument it plans for the default cycle)
 constexpr size_t TAIL_LDS_LIMIT = 150 * 1024;

@@ -6,6 +6,8 @@ Mirrors the Multigrid MC part of the reference's driver (src/driver_mgmc.cc):
   * measure_sampling_time: fix f = Q mean_x, nwarmup + nsamples cycles, QoI z = b^T x per
     sample, "time per sample", timeseries_multigridmc.txt, mean / variance against the exact
     observed mean and variance ......................................................... :40-107
+    (--energy-stride S: also the whole-field energy x^T Q x, f^T x of every S-th of those samples, reduced
+    on the device, to energy_multigridmc.txt, and the chi-square check of its mean; not in the reference)
   * measure_convergence: nsamplesconvergence chains from x = 0, nstepsconvergence cycles
     each; |E[z^k] - E[z]| and |Var[z^k] - Var[z]| with error bars to
     convergence_multigridmc.txt ........................................................ :188-314
@@ -96,9 +98,48 @@ def _qoi_series(sampler: MultigridMCSampler, nsteps: int, rows, vals) -> np.ndar
     return sampler.sample(nsteps, mg_native.QOI_VECTOR)
 
 
+def _iact_windowed(z) -> float:
+    """integrated autocorrelation time of a series: 1 + 2 sum of the autocorrelations down to the first below 0.05"""
+    z = np.asarray(z, dtype=np.float64) - np.mean(z)
+    var = z.var()
+    tau = 1.0
+    for t in range(1, len(z) // 10):
+        rho = np.dot(z[:-t], z[t:]) / ((len(z) - t) * var)
+        if rho < 0.05:
+            break
+        tau += 2 * rho
+    return tau
+
+
+def report_energy(sampler, label: str, f, mean_x_exact, filename: str = "energy_multigridmc.txt"):
+    """The recorded whole-field energy (MultigridMCSampler.energy_record): (cycle, xqx, fx) per record to
+    `filename`, and E = xqx - 2 fx + f^T Q^-1 f against chi-square with N degrees of freedom: its mean, N and the
+    z-score (mean - N) / sqrt(2 N tau / n), tau the windowed autocorrelation time of the records (at least 1).
+    f = Q mean_x_exact (measure_sampling_time), so f^T Q^-1 f = f^T mean_x_exact with the solve of mgmc_solve."""
+    info = sampler.energy_record_info()
+    xqx, fx = sampler.energy_series(0)
+    with open(filename, "w") as out:
+        for r in range(len(xqx)):
+            out.write(f"{(r + 1) * info['stride']:d} {xqx[r]:.17g} {fx[r]:.17g}\n")
+    const = float(np.dot(f, mean_x_exact))
+    e = xqx - 2.0 * fx + const
+    n, N = len(e), sampler.ndof
+    if n == 0:
+        print(f"  {label:>12s} energy   : no cycle recorded")
+        return None
+    tau = max(1.0, _iact_windowed(e)) if n >= 20 else 1.0
+    z = (e.mean() - N) / np.sqrt(2.0 * N * tau / n)
+    print(f"  {label:>12s} energy   = {e.mean():12.6e} over {n} records (x^T Q x - 2 f^T x + f^T Q^-1 f, "
+          f"f^T Q^-1 f = {const:.6e})")
+    print(f"  {'chi-square':>12s} N        = {N:12d}   z-score = {z:+.2f}   [tau = {tau:.2f}]")
+    return float(e.mean()), N, float(z)
+
+
 def measure_sampling_time(sampler, exact: ExactTargets, sampling_params: SamplingParameters,
-                          measurement_params: MeasurementParameters, label: str, filename: str):
-    """driver_mgmc.cc:40-107."""
+                          measurement_params: MeasurementParameters, label: str, filename: str,
+                          energy_stride=None):
+    """driver_mgmc.cc:40-107.  energy_stride=S (--energy-stride S): the energy of every S-th sample is recorded on
+    the device (report_energy)."""
     op = sampler.get_linear_operator()
     y = _measured_values(measurement_params)
     mean_x_exact = exact.posterior_mean(y) if op.get_m_lowrank() > 0 else np.zeros(op.get_ndof())
@@ -107,10 +148,17 @@ def measure_sampling_time(sampler, exact: ExactTargets, sampling_params: Samplin
     sampler.fix_rhs(f)
     sampler.set_state(np.zeros(op.get_ndof()))
     _qoi_series(sampler, sampling_params.nwarmup, rows, vals)
+    if energy_stride is not None:
+        sampler.energy_record(energy_stride, max(1, sampling_params.nsamples // energy_stride))
     t0 = time.perf_counter()
     data = _qoi_series(sampler, sampling_params.nsamples, rows, vals)
     t_elapsed = (time.perf_counter() - t0) * 1e3 / sampling_params.nsamples
     print(f"  {label:>12s} time per sample = {t_elapsed:12.4f} ms")
+    if energy_stride is not None:
+        try:
+            report_energy(sampler, label, f, mean_x_exact)
+        finally:
+            sampler.energy_record_off()
     with open(filename, "w") as out:
         for v in data:
             out.write(f"{v:g}\n")
@@ -243,14 +291,17 @@ def main(argv=None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
     batch = 1
     stderr_batch = None
-    while len(argv) >= 3 and argv[0] in ("--convergence-batch", "--stderr-batch"):
+    energy_stride = None
+    while len(argv) >= 3 and argv[0] in ("--convergence-batch", "--stderr-batch", "--energy-stride"):
         if argv[0] == "--convergence-batch":  # concurrent measure_convergence chains
             batch = int(argv[1])
+        elif argv[0] == "--energy-stride":  # measure_sampling_time: x^T Q x, f^T x of every S-th sample
+            energy_stride = int(argv[1])
         else:  # posterior_statistics: batch means of this many cycles (mean_stderr and iact in posterior.vtk)
             stderr_batch = int(argv[1])
         argv = argv[2:]
     if len(argv) != 1:
-        print(f"Usage: {sys.argv[0]} [--convergence-batch N] [--stderr-batch B] CONFIGURATIONFILE")
+        print(f"Usage: {sys.argv[0]} [--convergence-batch N] [--stderr-batch B] [--energy-stride S] CONFIGURATIONFILE")
         return -1
     t_start = time.time()
     print("\n+--------------------------------+")
@@ -323,7 +374,7 @@ def main(argv=None) -> int:
     if general.do_multigridmc:
         print("**** Multigrid MC ****")
         measure_sampling_time(sampler, exact, sampling_params, measurement_params, "MGMC",
-                              "timeseries_multigridmc.txt")
+                              "timeseries_multigridmc.txt", energy_stride)
         measure_convergence(sampler, exact, sampling_params, measurement_params, "convergence_multigridmc.txt",
                             batch)
         if general.save_posterior_statistics:

@@ -677,6 +677,55 @@ class MultigridMCSampler:
         B K (bM2 / (nb - 1)) / (M2 / (n - 1)).  ValueError with fewer than two completed batches."""
         return self._batch_means()[0][1]
 
+    # -- whole-field energy x^T Q x, f^T x, reduced on the device (mgmc_energy*, DESIGN.md 3k) --
+    def energy(self, chain=None, general: bool = False):
+        """(xqx, fx) of the current device state: xqx = x^T A x + sum_k (B_k^T x)^2 / Sigma_k and fx = f^T x with
+        the resident right-hand side (+0.0 while it is zero).  chain=None: two arrays of nchains values; a chain
+        index: two floats.  general=True takes the general kernel on a level that has the z-marching one.
+        E = xqx - 2 fx (+ f^T Q^-1 f) is chi-square with ndof degrees of freedom at stationarity."""
+        q, g = np.empty(self.nchains), np.empty(self.nchains)
+        self._chk(self.lib.mgmc_energy(self.handle, 1 if general else 0, _dp(q), _dp(g)))
+        if chain is None:
+            return q, g
+        return float(q[int(chain)]), float(g[int(chain)])
+
+    def energy_record(self, stride: int = 1, capacity: int = 4096):
+        """From now on every stride-th cycle (numbered 1, 2, ... from this call), whichever call runs it, records
+        (xqx, fx) of every chain on the device: the series keeps the first `capacity` records, the moments of
+        E = xqx - 2 fx keep counting.  On a sampler that already records: a reset with the new stride."""
+        self._chk(self.lib.mgmc_energy_record_enable(self.handle, int(stride), int(capacity)))
+        self._energy_capacity = int(capacity)
+
+    def energy_record_off(self):
+        """Free the record; the cycle is again the one of a sampler that never recorded."""
+        self._chk(self.lib.mgmc_energy_record_disable(self.handle))
+
+    def reset_energy_record(self):
+        """Zero the moments, the record count and the cycle count of the thinning."""
+        self._chk(self.lib.mgmc_energy_record_reset(self.handle))
+
+    def energy_record_info(self) -> dict:
+        """{"enabled": bool, "stride": int (0 while disabled), "ncycles": cycles seen, "nrecorded": cycles
+        recorded since the enable / reset}"""
+        en, st, nc, nr = ctypes.c_int(), ctypes.c_int(), ctypes.c_uint64(), ctypes.c_uint64()
+        self._chk(self.lib.mgmc_energy_record_info(self.handle, ctypes.byref(en), ctypes.byref(st), ctypes.byref(nc),
+                                                   ctypes.byref(nr)))
+        return {"enabled": bool(en.value), "stride": st.value, "ncycles": nc.value, "nrecorded": nr.value}
+
+    def energy_series(self, chain: int = 0):
+        """(xqx, fx): the records kept for one chain (the first `capacity` of them), two arrays."""
+        info = self.energy_record_info()
+        n = min(info["nrecorded"], self._energy_capacity) if info["enabled"] else 0
+        q, g = np.empty(n), np.empty(n)
+        self._chk(self.lib.mgmc_energy_get_series(self.handle, int(chain), _dp(q), _dp(g), n))
+        return q, g
+
+    def energy_moments(self, chain: int = 0):
+        """(n, mean, M2) of E = xqx - 2 fx over the recorded cycles of one chain."""
+        out = np.zeros(3)
+        self._chk(self.lib.mgmc_energy_moments(self.handle, int(chain), _dp(out)))
+        return out
+
     def get_series(self, n: int, chain: int = 0) -> np.ndarray:
         """The QoI series of the last sample / sample_async call (waits for this handle's stream)."""
         out = np.empty(max(int(n), 0))
