@@ -331,7 +331,8 @@ int mgmc_get_stream(mgmc_handle* h, void** stream);
  * One mean and one M2 field per handle whatever nchains is (the chains sample the same distribution);
  * the reference's variance E[x^2] - mean^2 is M2 / nrecorded.  The fields stay in HBM (two vectors in the
  * fine level's padded layout) until mgmc_field_stats_get.  mgmc_set_state, mgmc_set_rhs and
- * mgmc_set_sample_index do not reset them; mgmc_set_lowrank and mgmc_set_qoi_vector keep them recording.
+ * mgmc_set_sample_index do not reset them; mgmc_set_lowrank and mgmc_set_qoi_vector keep them recording
+ * (mgmc_set_lowrank resets them in the Rao-Blackwellised mode below).
  * Disabled (the default) the cycle and its graphs are those of a handle that never enabled them.
  * MGMC_E_INVALID: a NULL handle, stride < 1, a wrong n, get / reset while disabled; MGMC_E_NOMEM: the
  * fields could not be allocated (the handle stays disabled and otherwise intact). */
@@ -368,6 +369,36 @@ int mgmc_field_stats_batch_info(const mgmc_handle* h, int* batch, uint64_t* nbat
 int mgmc_field_stats_get_batch(mgmc_handle* h, double* bmean, double* bm2, size_t n);
                                                           /* reference layout, n = ndof; either pointer may be NULL;
                                                              waits for the handle's stream */
+/* Rao-Blackwellised statistics: for x ~ N(Q^{-1} f, Q^{-1}) the law of one vertex given the rest is
+ * N(c_i, 1 / d_i) with d_i = Q_ii and c = x + D^{-1} (f - Q x), one Jacobi step applied to the sample.
+ * E[c] = Q^{-1} f and diag Cov(c) = diag(Q^{-1}) - D^{-1}: mean(c) estimates the posterior mean and
+ * 1 / d_i + var(c_i) the marginal variance, with only the smaller part of the variance left to Monte Carlo.
+ * The identity needs only that every state has the target law, so it holds along a correlated chain.
+ * In this mode the fields above (and the batch fields when batch >= 1) fold c in place of x, with the same
+ * statements and chain order.  Per recorded state, at every interior vertex of level 0, in plain IEEE double:
+ *     y_i = (Q x)_i   the bits of mgmc_operator_apply(h, 0, x) (the low-rank patch included),
+ *     c_i = x_i + (f_i - y_i) / d_i,   f the vector of mgmc_set_rhs (+0.0 while it is all +0.0),
+ *     d_i = a_ii, then for k = 0 .. m-1 ascending with B_ik stored:  d_i = d_i + (B_ik * B_ik) / Sigma_k.
+ * Two paths compute the same bits: one fused z-marching kernel (one chain on a level that runs the z-sweep
+ * with a constant stencil and no low-rank part), and everywhere else two passes (c into a buffer of
+ * nchains x nstore doubles, then the plain fold).  MGMC_FIELD_COND_TWO_PASS takes the two passes where the
+ * plan would fuse (how the two are compared).  disable, reset, info, get, batch_info and get_batch work as
+ * above; mgmc_field_stats_enable / _enable_batched on a conditional handle switch back to plain statistics
+ * (a reset).  mgmc_set_rhs, mgmc_set_state, mgmc_set_sample_index and mgmc_set_qoi_vector do not reset.
+ * mgmc_set_lowrank changes d and Q: on a conditional handle it plans the path again, rebuilds d and RESETS
+ * the statistics (n = 0, a partial batch dropped); if that needs an allocation which fails, the statistics
+ * are left disabled and the call returns the error code.
+ * MGMC_E_INVALID: a NULL handle, stride < 1, batch < 0, unknown flag bits, a wrong n, get_cond_precision while
+ * the mode is off; MGMC_E_NOMEM: an allocation failed (the handle stays as it was before the call). */
+#define MGMC_FIELD_COND_TWO_PASS 1u
+int mgmc_field_stats_enable_cond(mgmc_handle* h, int stride, int batch, unsigned flags);
+                                                          /* batch 0: no batch means.  On an enabled handle: a
+                                                             reset, with a graph rebuild where the mode or the
+                                                             instance changes */
+int mgmc_field_stats_cond_info(const mgmc_handle* h, int* enabled, int* path);
+                                                          /* path: 0 off / plain, 1 fused z-march, 2 two-pass */
+int mgmc_field_stats_get_cond_precision(mgmc_handle* h, double* d, size_t n);
+                                                          /* d in the reference layout, n = ndof */
 
 /* ---- whole-field energy: x^T Q x and f^T x of the level-0 state, reduced on the device ----
  * Per chain two doubles:

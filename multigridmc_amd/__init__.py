@@ -27,6 +27,7 @@ from .sampler import (  # noqa: F401
     ConstantCorrelationLengthModel,
     PeriodicCorrelationLengthModel,
     batch_means_estimates,
+    rao_blackwell_estimates,
     comm_unique_id,
     csr_colour_scheme,
     describe,

@@ -130,6 +130,9 @@ SIGNATURES = [
     ("mgmc_field_stats_enable_batched", c_int, [_H, c_int, c_int]),
     ("mgmc_field_stats_batch_info", c_int, [_H, POINTER(c_int), POINTER(c_uint64)]),
     ("mgmc_field_stats_get_batch", c_int, [_H, _DP, _DP, c_size_t]),
+    ("mgmc_field_stats_enable_cond", c_int, [_H, c_int, c_int, ctypes.c_uint]),
+    ("mgmc_field_stats_cond_info", c_int, [_H, POINTER(c_int), POINTER(c_int)]),
+    ("mgmc_field_stats_get_cond_precision", c_int, [_H, _DP, c_size_t]),
     ("mgmc_energy", c_int, [_H, ctypes.c_uint, _DP, _DP]),
     ("mgmc_energy_record_enable", c_int, [_H, c_int, c_int64]),
     ("mgmc_energy_record_disable", c_int, [_H]),

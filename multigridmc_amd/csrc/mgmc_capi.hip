@@ -1875,6 +1875,50 @@ static void launch_energy(mgmc_handle* h, bool general, uint64_t* ctl, hipStream
                        (const double*)lv.lr.sc_inv, lv.lr.m, h->en_out, ctl, h->en_sq, h->en_sf, h->en_mom);
 }
 
+// ---- Rao-Blackwellised field statistics (mgmc_fieldcond.hpp): c of level 0's canonical buffer, folded into the
+// fields of mgmc_field_stats_* ----
+// f is level 0's own buffer (the user's values at the end of a cycle, see launch_energy); FZ as there.
+static void launch_fieldcond(mgmc_handle* h, hipStream_t s) {
+    const Level& lv = h->levels[0];
+    const int nch = h->nchains;
+    const bool fz = h->f0_zero;
+    const long long cs = lv.L.nstore;
+    if (h->fc_path == FieldCondPath::FUSED) {  // (one chain, constant 7-point stencil, no low-rank part)
+        FieldCondZArgs a;
+        a.L = lv.L;
+        a.x = lv.x;
+        a.f = lv.f;
+        a.a[0] = lv.S.a[4], a.a[1] = lv.S.a[10], a.a[2] = lv.S.a[12], a.a[3] = lv.S.a[13];
+        a.a[4] = lv.S.a[14], a.a[5] = lv.S.a[16], a.a[6] = lv.S.a[22];
+        a.d = lv.S.a[13];
+        a.mean = h->fs_mean, a.m2 = h->fs_m2;
+        a.bsum = h->fs_bsum, a.bmean = h->fs_bmean, a.bm2 = h->fs_bm2;
+        a.ctl = h->fs_ctl;
+        lds_poison(h, lv, s);
+        launch_fieldcond_z(a, fz, h->fs_ctl, s);
+        return;
+    }
+    // two-pass: y of every chain (mgmc_operator_apply's launches, chain by chain: the low-rank dots are one
+    // chain's), c in place over it, then the fold of plain statistics
+    for (int c = 0; c < nch; ++c) {
+        lds_poison(h, lv, s);
+        launch_operator_apply(h, lv, lv.x + c * cs, h->fc_buf + c * cs, s);
+    }
+    const int dim = lv.spec.dim, nplanes = dim == 3 ? lv.L.nz - 1 : 1;
+    const dim3 block(64, 4, 1);
+    const dim3 grid = grid3(lv.L.nx - 1, lv.L.ny - 1, nplanes * nch, block);
+    const double dscal = lv.S.a[dim == 3 ? 13 : 4];
+#define FC_LAUNCH_C(D, Z)                                                                                        \
+    hipLaunchKernelGGL((k_fieldcond_c<D, Z>), grid, block, 0, s, lv.L, (const double*)lv.x, (const double*)lv.f, \
+                       h->fc_buf, (const double*)h->fc_d, dscal, cs, nplanes, (const uint64_t*)h->fs_ctl)
+    if (dim == 3 && fz) FC_LAUNCH_C(3, true);
+    else if (dim == 3) FC_LAUNCH_C(3, false);
+    else if (fz) FC_LAUNCH_C(2, true);
+    else FC_LAUNCH_C(2, false);
+#undef FC_LAUNCH_C
+    launch_fieldstats(h->fc_buf, cs, nch, h->fs_mean, h->fs_m2, h->fs_ctl, s, h->fs_bsum, h->fs_bmean, h->fs_bm2);
+}
+
 void enqueue_ops(mgmc_handle* h, size_t begin, size_t end, hipStream_t s) {
     const uint64_t* sample = h->ctrl;  // ctrl[0]
     const int nch = h->nchains;        // batched chains: every launch covers all of them
@@ -2019,6 +2063,10 @@ void enqueue_ops(mgmc_handle* h, size_t begin, size_t end, hipStream_t s) {
                 break;
             }
             case OP_FIELDSTATS: {  // level 0's canonical buffer holds the cycle's state (OP_COPY before OP_QOI)
+                if (h->fc_on) {  // Rao-Blackwellised: the conditional mean c in x's place
+                    launch_fieldcond(h, s);
+                    break;
+                }
                 launch_fieldstats(h->levels[0].x, (long long)h->levels[0].L.nstore, nch, h->fs_mean, h->fs_m2,
                                   h->fs_ctl, s, h->fs_bsum, h->fs_bmean, h->fs_bm2);
                 break;
@@ -2799,6 +2847,8 @@ int mgmc_destroy(mgmc_handle* h) {
     if (h->fs_bsum) hipFree(h->fs_bsum);
     if (h->fs_bmean) hipFree(h->fs_bmean);
     if (h->fs_bm2) hipFree(h->fs_bm2);
+    if (h->fc_buf) hipFree(h->fc_buf);
+    if (h->fc_d) hipFree(h->fc_d);
     if (h->en_part) hipFree(h->en_part);
     if (h->en_part2) hipFree(h->en_part2);
     if (h->en_out) hipFree(h->en_out);
@@ -2939,7 +2989,8 @@ int mgmc_set_rhs(mgmc_handle* h, const double* f, size_t n) {
     if (zero != h->f0_zero) {
         h->f0_zero = zero;
         // (a recording energy op reads f0_zero too: its FZ instances, mgmc_energy.hpp)
-        if (mark_rhs_zero(h) || h->en_ctl) return build_graphs(h);
+        // (... and the Rao-Blackwellised field statistics, mgmc_fieldcond.hpp)
+        if (mark_rhs_zero(h) || h->en_ctl || h->fc_on) return build_graphs(h);
     }
     return MGMC_OK;
 }
@@ -3526,7 +3577,18 @@ static void fieldstats_free_batch(mgmc_handle* h) {
     h->fs_batch = 0;
 }
 
+// the conditional mode's buffers (the fields themselves stay)
+static void fieldcond_free(mgmc_handle* h) {
+    if (h->fc_buf) hipFree(h->fc_buf);
+    if (h->fc_d) hipFree(h->fc_d);
+    h->fc_buf = h->fc_d = nullptr;
+    h->fc_on = false;
+    h->fc_flags = 0;
+    h->fc_path = FieldCondPath::TWO_PASS;
+}
+
 static void fieldstats_free(mgmc_handle* h) {
+    fieldcond_free(h);
     if (h->fs_mean) hipFree(h->fs_mean);
     if (h->fs_m2) hipFree(h->fs_m2);
     if (h->fs_ctl) hipFree(h->fs_ctl);
@@ -3560,8 +3622,10 @@ int mgmc_field_stats_enable(mgmc_handle* h, int stride) {
     if (stride < 1) return fail(h, MGMC_E_INVALID, "field statistics: stride must be >= 1");
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->fs_bsum) {  // batched: back to the kernel without batching (the graphs hold the batch fields' addresses)
+    if (h->fs_bsum || h->fc_on) {  // batched or conditional: back to the plain kernel without batching (the graphs
+                                   // hold the batch fields' addresses and the conditional launches)
         destroy_graphs(h);
+        fieldcond_free(h);
         fieldstats_free_batch(h);
         return fieldstats_start(h, stride, 0);
     }
@@ -3582,6 +3646,12 @@ int mgmc_field_stats_enable_batched(mgmc_handle* h, int stride, int batch) {
     if (batch < 1) return fail(h, MGMC_E_INVALID, "field statistics: batch must be >= 1");
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    const bool was_cond = h->fc_on;
+    if (was_cond) {  // conditional: back to plain statistics (a reset; the graphs hold the conditional launches)
+        destroy_graphs(h);
+        fieldcond_free(h);
+        if (h->fs_bsum) return fieldstats_start(h, stride, batch);
+    }
     if (h->fs_bsum) return fieldstats_zero(h, stride, batch);  // batched: a reset with both (same graphs)
     // the fields the handle lacks: all five and the counters, or the three batch fields of an enabled handle;
     // the handle takes them only once all are there
@@ -3685,6 +3755,174 @@ int mgmc_field_stats_get_batch(mgmc_handle* h, double* bmean, double* bm2, size_
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return MGMC_OK;
 }
+
+// ---------------- Rao-Blackwellised field statistics (mgmc_fieldcond.hpp) ----------------
+
+// what the conditional mode needs besides the fields: the path, the two-pass buffer and the d-field
+struct FieldCondSetup {
+    FieldCondPath path = FieldCondPath::TWO_PASS;
+    double* buf = nullptr;  // new allocations only (nullptr: none needed, or the handle's is kept)
+    double* d = nullptr;
+    bool need_d = false;
+};
+
+// plans the path for the handle as it is and allocates what the handle lacks for it (the d-field is always built
+// anew); MGMC_E_NOMEM / MGMC_E_HIP free what was allocated here and leave the handle as it was
+static int fieldcond_prepare(mgmc_handle* h, unsigned flags, FieldCondSetup* out) {
+    Level& lv = h->levels[0];
+    FieldCondSetup su;
+    su.path = plan_fieldcond(lv.shape, lv.paths, h->nchains, lv.lr.m > 0, (flags & MGMC_FIELD_COND_TWO_PASS) != 0);
+    su.need_d = lv.field || lv.lr.m > 0;
+    const size_t bytes = (size_t)lv.L.nstore * sizeof(double);
+    auto bail = [&](int code, const char* msg) {
+        (void)hipGetLastError();
+        if (su.buf) hipFree(su.buf);
+        if (su.d) hipFree(su.d);
+        return fail(h, code, msg);
+    };
+    if (su.path == FieldCondPath::TWO_PASS && !h->fc_buf) {
+        if (hipMalloc(&su.buf, bytes * h->nchains) != hipSuccess)
+            return bail(MGMC_E_NOMEM, "device allocation failed (conditional field statistics)");
+        if (hipMemsetAsync(su.buf, 0, bytes * h->nchains, h->stream) != hipSuccess)
+            return bail(MGMC_E_HIP, "conditional field statistics: zeroing the buffer failed");
+    }
+    if (su.need_d) {
+        if (hipMalloc(&su.d, bytes) != hipSuccess)
+            return bail(MGMC_E_NOMEM, "device allocation failed (conditional field statistics)");
+        if (hipMemsetAsync(su.d, 0, bytes, h->stream) != hipSuccess)
+            return bail(MGMC_E_HIP, "conditional field statistics: zeroing the d-field failed");
+        const size_t n = lv.spec.ndof;
+        std::vector<double> d;
+        try {
+            d.assign(n, lv.S.a[lv.spec.dim == 3 ? 13 : 4]);
+        } catch (const std::bad_alloc&) {
+            return bail(MGMC_E_NOMEM, "host allocation failed (conditional field statistics)");
+        }
+        if (lv.field) {  // the diagonal of the coefficient field, through the d-field's own storage
+            const dim3 block(64, 4, 1);
+            const dim3 grid = grid3(lv.L.nx - 1, lv.L.ny - 1, lv.spec.dim == 3 ? lv.L.nz - 1 : 1, block);
+            if (lv.spec.dim == 3) hipLaunchKernelGGL(k_fieldcond_diag<3>, grid, block, 0, h->stream, lv.L, lv.F, su.d);
+            else hipLaunchKernelGGL(k_fieldcond_diag<2>, grid, block, 0, h->stream, lv.L, lv.F, su.d);
+            if (download(h, 0, su.d, d.data()) != MGMC_OK || hipStreamSynchronize(h->stream) != hipSuccess)
+                return bail(MGMC_E_HIP, "conditional field statistics: reading the diagonal failed");
+        }
+        if (lv.lr.m > 0)
+            fieldcond_precision(d.data(), n, lv.lr.m, h->lr0_colptr.data(), h->lr0_rows.data(), h->lr0_vals.data(),
+                                h->lr0_sigma.data());
+        if (upload(h, 0, d.data(), su.d) != MGMC_OK || hipStreamSynchronize(h->stream) != hipSuccess)
+            return bail(MGMC_E_HIP, "conditional field statistics: writing the d-field failed");
+    }
+    *out = su;
+    return MGMC_OK;
+}
+
+// the handle takes a prepared setup (buffers the new path does not need are freed)
+static void fieldcond_commit(mgmc_handle* h, unsigned flags, const FieldCondSetup& su) {
+    if (su.buf) h->fc_buf = su.buf;
+    if (su.path == FieldCondPath::FUSED && h->fc_buf) {
+        hipFree(h->fc_buf);
+        h->fc_buf = nullptr;
+    }
+    if (h->fc_d) hipFree(h->fc_d);
+    h->fc_d = su.d;
+    h->fc_path = su.path;
+    h->fc_flags = flags;
+    h->fc_on = true;
+}
+
+int mgmc_field_stats_enable_cond(mgmc_handle* h, int stride, int batch, unsigned flags) {
+    if (!h) return fail(nullptr, MGMC_E_INVALID, "null handle");
+    if (stride < 1) return fail(h, MGMC_E_INVALID, "field statistics: stride must be >= 1");
+    if (batch < 0) return fail(h, MGMC_E_INVALID, "field statistics: batch must be >= 0");
+    if (flags & ~(unsigned)MGMC_FIELD_COND_TWO_PASS) return fail(h, MGMC_E_INVALID, "field statistics: unknown flag");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    // conditional already, the same instance: a reset (same graphs)
+    if (h->fc_on && h->fc_flags == flags && (batch > 0) == (h->fs_bsum != nullptr)) return fieldstats_zero(h, stride, batch);
+    FieldCondSetup su;
+    int rc = fieldcond_prepare(h, flags, &su);
+    if (rc) return rc;
+    // the fields the handle lacks; it takes them only once all are there
+    const size_t bytes = (size_t)h->levels[0].L.nstore * sizeof(double);
+    const bool enabled = h->fs_mean != nullptr, batched = h->fs_bsum != nullptr;
+    double* f[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    uint64_t* ctl = nullptr;
+    bool ok = true;
+    for (int q = 0; q < 5 && ok; ++q)
+        if (q < 2 ? !enabled : (batch > 0 && !batched)) ok = hipMalloc(&f[q], bytes) == hipSuccess;
+    if (ok && !enabled) ok = hipMalloc(&ctl, FS_CTL_WORDS * sizeof(uint64_t)) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        for (double* p : f)
+            if (p) hipFree(p);
+        if (ctl) hipFree(ctl);
+        if (su.buf) hipFree(su.buf);
+        if (su.d) hipFree(su.d);
+        return fail(h, MGMC_E_NOMEM, "device allocation failed (conditional field statistics)");
+    }
+    destroy_graphs(h);  // (an enabled handle's hold the plain launches or the other instance)
+    if (!enabled) {
+        h->fs_mean = f[0];
+        h->fs_m2 = f[1];
+        h->fs_ctl = ctl;
+    }
+    if (batch > 0 && !batched) {
+        h->fs_bsum = f[2];
+        h->fs_bmean = f[3];
+        h->fs_bm2 = f[4];
+    }
+    if (batch == 0 && batched) fieldstats_free_batch(h);
+    fieldcond_commit(h, flags, su);
+    return fieldstats_start(h, stride, batch);
+}
+
+int mgmc_field_stats_cond_info(const mgmc_handle* h, int* enabled, int* path) {
+    if (!h) return fail(nullptr, MGMC_E_INVALID, "null handle");
+    if (enabled) *enabled = h->fc_on ? 1 : 0;
+    if (path) *path = h->fc_on ? (int)h->fc_path : 0;
+    return MGMC_OK;
+}
+
+int mgmc_field_stats_get_cond_precision(mgmc_handle* h, double* d, size_t n) {
+    if (!h) return fail(nullptr, MGMC_E_INVALID, "null handle");
+    if (!h->fc_on)
+        return fail(h, MGMC_E_INVALID, "conditional field statistics are not enabled (mgmc_field_stats_enable_cond)");
+    if (!d) return fail(h, MGMC_E_INVALID, "null argument");
+    const Level& lv = h->levels[0];
+    if (n != lv.spec.ndof) return fail(h, MGMC_E_INVALID, "field statistics size mismatch");
+    if (!h->fc_d) {  // the centre coefficient at every vertex
+        std::fill(d, d + n, lv.S.a[lv.spec.dim == 3 ? 13 : 4]);
+        return MGMC_OK;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = download(h, 0, h->fc_d, d);
+    if (rc) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MGMC_OK;
+}
+
+extern "C++" {
+namespace mgmc_host {
+// mgmc_set_lowrank on a conditional handle, after the levels' low-rank parts changed and before the op list and
+// the graphs are rebuilt: d and Q changed, so the path is planned again, d rebuilt and the statistics reset.  A
+// failure leaves the statistics disabled and returns the error code.
+int fieldcond_lowrank_changed(mgmc_handle* h) {
+    if (!h->fc_on) return MGMC_OK;
+    FieldCondSetup su;
+    int rc = fieldcond_prepare(h, h->fc_flags, &su);
+    if (rc == MGMC_OK) {
+        fieldcond_commit(h, h->fc_flags, su);
+        rc = fieldstats_zero(h, h->fs_stride, h->fs_batch);
+    }
+    if (rc != MGMC_OK) {
+        const std::string err = h->last_error;
+        fieldstats_free(h);
+        return fail(h, rc, err);
+    }
+    return MGMC_OK;
+}
+}  // namespace mgmc_host
+}  // extern "C++"
 
 // ---------------- whole-field energy x^T Q x, f^T x (mgmc_energy.hpp) ----------------
 

@@ -49,6 +49,8 @@ static_assert(MGMC_LAYOUT_POINT == mgmc::LF_POINT && MGMC_LAYOUT_PAIRS == mgmc::
 #include "mgmc_rhs_zero.hpp"
 #include "mgmc_fieldstats.hpp"
 #include "mgmc_energy.hpp"
+#include "mgmc_fieldcond.hpp"
+#include "mgmc_fieldcond_host.hpp"
 
 using namespace mgmc;
 
@@ -264,6 +266,17 @@ struct mgmc_handle {
     double* fs_bmean = nullptr;     // Welford mean and M2 of the completed batches' means
     double* fs_bm2 = nullptr;
     int fs_batch = 0;               // batch length in recorded cycles (0: no batching)
+    // Rao-Blackwellised statistics (mgmc_field_stats_enable_cond, mgmc_fieldcond.hpp): the fields above fold the
+    // conditional mean c instead of x while fc_on holds (then fs_mean != nullptr too)
+    bool fc_on = false;
+    unsigned fc_flags = 0;          // MGMC_FIELD_COND_* of the enable call
+    FieldCondPath fc_path = FieldCondPath::TWO_PASS;  // plan_fieldcond's choice
+    double* fc_buf = nullptr;       // two-pass: y, then c of every chain (nchains x L.nstore; halo and padding 0)
+    double* fc_d = nullptr;         // the d-field (padded layout; per-vertex coefficients or a low-rank part),
+                                    // nullptr: d is level 0's centre coefficient
+    // level 0's low-rank part as mgmc_set_lowrank received it (CSC), for d
+    std::vector<int64_t> lr0_colptr, lr0_rows;
+    std::vector<double> lr0_vals, lr0_sigma;
     // whole-field energy (mgmc_energy*, mgmc_energy.hpp).  The reduction scratch is allocated by the first call
     // that needs it and kept: workgroup partials, their block sums, the chains' (xqx, fx)
     double2* en_part = nullptr;
@@ -388,6 +401,7 @@ Layout tail_layout(const Layout& L);
 void build_ops(mgmc_handle* h);
 int build_tails(mgmc_handle* h);
 void sync_fieldstats_op(mgmc_handle* h);
+int fieldcond_lowrank_changed(mgmc_handle* h);
 bool mark_rhs_zero(mgmc_handle* h);
 int build_graphs(mgmc_handle* h);
 void destroy_graphs(mgmc_handle* h);

@@ -306,6 +306,21 @@ inline EnergyPlan plan_energy(const LevelShape& sh, uint32_t paths, bool force_g
     return p;
 }
 
+// ---- the Rao-Blackwellised field statistics of level 0 (mgmc_fieldcond.hpp) ----
+enum class FieldCondPath {
+    FUSED = 1,     // k_fieldcond_z: stencil and Welford fold in one z-march
+    TWO_PASS = 2,  // operator apply + k_fieldcond_c into the c buffer, then k_fieldstats on it
+};
+// The fused z-march goes where level 0 runs the z-sweep with a constant stencil (not the variable-diagonal
+// instance), has no low-rank part and the handle one chain; force_two_pass: MGMC_FIELD_COND_TWO_PASS, the two-pass
+// path on such a level (how the two are compared).
+inline FieldCondPath plan_fieldcond(const LevelShape& sh, uint32_t paths, int nchains, bool lowrank,
+                                    bool force_two_pass) {
+    const bool fused = plan_sweep(sh, paths, 0, -1) == SweepKernel::ZSWEEP && !sh.field && !lowrank && nchains == 1 &&
+                       !force_two_pass;
+    return fused ? FieldCondPath::FUSED : FieldCondPath::TWO_PASS;
+}
+
 // ---- the coarsest levels' sub-cycle in one workgroup (k_tail) ----
 // (tail_start below; without a run_ops argument it plans for the default cycle)
 constexpr size_t TAIL_LDS_LIMIT = 150 * 1024;

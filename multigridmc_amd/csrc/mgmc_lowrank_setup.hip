@@ -375,9 +375,15 @@ int mgmc_set_lowrank(mgmc_handle* h, int m, const int64_t* colptr, const int64_t
     }
     h->lr_cols.clear();
     h->lr_sigma.clear();
+    h->lr0_colptr.clear(), h->lr0_rows.clear(), h->lr0_vals.clear(), h->lr0_sigma.clear();
     if (!rc && m > 0) {
         h->lr_cols = cols;
         h->lr_sigma.assign(sigma, sigma + m);
+        // level 0's B as given, for the conditional precision of the Rao-Blackwellised field statistics
+        h->lr0_colptr.assign(colptr, colptr + m + 1);
+        h->lr0_rows.assign(rows, rows + colptr[m]);
+        h->lr0_vals.assign(vals, vals + colptr[m]);
+        h->lr0_sigma.assign(sigma, sigma + m);
     }
     if (!rc && h->chol_n > 0)  // the coarse factors carry B_c Sigma^{-1} B_c^T
         rc = build_coarse_chol(h, m > 0 ? &cols : nullptr, sigma, m);
@@ -390,6 +396,7 @@ int mgmc_set_lowrank(mgmc_handle* h, int m, const int64_t* colptr, const int64_t
         for (auto& lv : h->levels) free_lowrank(lv.lr);
         h->lr_cols.clear();
         h->lr_sigma.clear();
+        h->lr0_colptr.clear(), h->lr0_rows.clear(), h->lr0_vals.clear(), h->lr0_sigma.clear();
         h->last_error = err;
         if (h->chol_n > 0 && build_coarse_chol(h, nullptr, nullptr, 0) != MGMC_OK) {
             // the prior's factor built at mgmc_create cannot be rebuilt (e.g. an allocation): no
@@ -401,11 +408,14 @@ int mgmc_set_lowrank(mgmc_handle* h, int m, const int64_t* colptr, const int64_t
         set_global_error(err);
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    // Rao-Blackwellised field statistics: d and Q changed, so the path is planned again, d rebuilt and the
+    // statistics reset (a failed allocation leaves them disabled) before the op list and the graphs are rebuilt
+    const int rc3 = fieldcond_lowrank_changed(h);
     build_ops(h);
     int rc2 = build_tails(h);
     if (!rc2) rc2 = build_graphs(h);
     if (!rc && !rc2) h->unusable = false;  // a later successful install rebuilt a whole coarse factor
-    return rc ? rc : rc2;
+    return rc ? rc : rc2 ? rc2 : rc3;
 }
 
 int mgmc_debug_fail_coarse_factor(mgmc_handle* h, int n) {

@@ -258,24 +258,32 @@ def measure_convergence(sampler, exact: ExactTargets, sampling_params: SamplingP
 
 
 def posterior_statistics(sampler, exact: ExactTargets, sampling_params: SamplingParameters,
-                         measurement_params: MeasurementParameters, stderr_batch=None):
+                         measurement_params: MeasurementParameters, stderr_batch=None, rao_blackwell=False):
     """driver_mgmc.cc:118-171: the sample mean and the pointwise variance of the field over nsamples
     cycles after nwarmup, to posterior.vtk with the exact mean (2D: the sample location's circle to
     sample_location.vtk).  The moments are accumulated on the device (field_stats): the state never
     leaves HBM.  stderr_batch=B (--stderr-batch B): batch means of B cycles on the device too, and
     posterior.vtk also carries mean_stderr, the Monte Carlo standard error of the mean field, and iact, the
-    integrated autocorrelation time per vertex; nsamples must hold at least two batches."""
+    integrated autocorrelation time per vertex; nsamples must hold at least two batches.
+    rao_blackwell=True (--rao-blackwell): the device folds the conditional mean c = x + D^-1 (f - Q x) of every
+    vertex given the rest in place of x; mean and variance are then the Rao-Blackwell estimates
+    (rao_blackwell_estimates), variance_conditional = 1 / diag(Q) is the part of the variance they know
+    exactly, and mean_stderr / iact describe the Rao-Blackwell mean."""
     op = sampler.get_linear_operator()
     y = _measured_values(measurement_params)
     mean_x_exact = exact.posterior_mean(y) if op.get_m_lowrank() > 0 else np.zeros(op.get_ndof())
     sampler.fix_rhs(sampler.operator_apply(0, mean_x_exact))
     sampler.set_state(np.zeros(op.get_ndof()))
     sampler.sample(sampling_params.nwarmup)
-    sampler.field_stats(1, batch=stderr_batch)
+    sampler.field_stats(1, batch=stderr_batch, conditional=rao_blackwell)
     fields = {"mean_exact": mean_x_exact}
     try:
         sampler.sample(sampling_params.nsamples)
-        fields["mean"], fields["variance"] = mean, variance = sampler.field_mean_variance()
+        if rao_blackwell:
+            fields["mean"], fields["variance"] = mean, variance = sampler.field_rb_mean_variance()
+            fields["variance_conditional"] = 1.0 / sampler.field_conditional_precision()
+        else:
+            fields["mean"], fields["variance"] = mean, variance = sampler.field_mean_variance()
         if stderr_batch is not None:
             fields["mean_stderr"] = sampler.field_mean_stderr()[1]
             fields["iact"] = sampler.field_iact()
@@ -292,7 +300,13 @@ def main(argv=None) -> int:
     batch = 1
     stderr_batch = None
     energy_stride = None
-    while len(argv) >= 3 and argv[0] in ("--convergence-batch", "--stderr-batch", "--energy-stride"):
+    rao_blackwell = False
+    while (len(argv) >= 3 and argv[0] in ("--convergence-batch", "--stderr-batch", "--energy-stride")) or \
+            (len(argv) >= 2 and argv[0] == "--rao-blackwell"):
+        if argv[0] == "--rao-blackwell":  # posterior_statistics: the Rao-Blackwell estimates of mean and variance
+            rao_blackwell = True
+            argv = argv[1:]
+            continue
         if argv[0] == "--convergence-batch":  # concurrent measure_convergence chains
             batch = int(argv[1])
         elif argv[0] == "--energy-stride":  # measure_sampling_time: x^T Q x, f^T x of every S-th sample
@@ -301,7 +315,8 @@ def main(argv=None) -> int:
             stderr_batch = int(argv[1])
         argv = argv[2:]
     if len(argv) != 1:
-        print(f"Usage: {sys.argv[0]} [--convergence-batch N] [--stderr-batch B] [--energy-stride S] CONFIGURATIONFILE")
+        print(f"Usage: {sys.argv[0]} [--convergence-batch N] [--stderr-batch B] [--energy-stride S] "
+              "[--rao-blackwell] CONFIGURATIONFILE")
         return -1
     t_start = time.time()
     print("\n+--------------------------------+")
@@ -378,8 +393,9 @@ def main(argv=None) -> int:
         measure_convergence(sampler, exact, sampling_params, measurement_params, "convergence_multigridmc.txt",
                             batch)
         if general.save_posterior_statistics:
-            posterior_statistics(sampler, exact, sampling_params, measurement_params, stderr_batch)
+            posterior_statistics(sampler, exact, sampling_params, measurement_params, stderr_batch, rao_blackwell)
             print("  posterior_statistics: mean, variance and mean_exact written to posterior.vtk"
+                  + ("; Rao-Blackwell estimates, with variance_conditional" if rao_blackwell else "")
                   + ("" if stderr_batch is None else f"; mean_stderr and iact from batches of {stderr_batch} cycles"))
         print()
     secs = int(time.time() - t_start)

@@ -384,6 +384,18 @@ def batch_means_estimates(states_per_batch, nb, bm2, n, m2):
     return np.sqrt(bvar / nb), iact
 
 
+def rao_blackwell_estimates(n, mean, m2, d):
+    """(mean, variance) of the Rao-Blackwellised field statistics, per vertex: mean and m2 are the running mean
+    and the sum of squared deviations of the n recorded conditional means c = x + D^-1 (f - Q x), d = diag(Q).
+        mean      estimates Q^-1 f          (E[c] = E[x])
+        variance  = 1 / d + m2 / n          (diag Cov(x) = D^-1 + diag Cov(c))
+    ValueError while n = 0."""
+    if n == 0:
+        raise ValueError("no state has been recorded yet")
+    mean, m2 = np.asarray(mean, dtype=np.float64), np.asarray(m2, dtype=np.float64)
+    return mean, 1.0 / np.asarray(d, dtype=np.float64) + m2 / n
+
+
 class MultigridMCSampler:
     """Device MGMC sampler with the reference's Sampler interface (sampler/sampler.hh:23-72).
 
@@ -604,14 +616,23 @@ class MultigridMCSampler:
         self._chk(self.lib.mgmc_reset_moments(self.handle))
 
     # -- pointwise field statistics on the device (posterior_statistics, driver_mgmc.cc:118-171) --
-    def field_stats(self, stride: int = 1, batch=None):
+    def field_stats(self, stride: int = 1, batch=None, conditional: bool = False, two_pass: bool = False):
         """From now on every stride-th cycle (numbered 1, 2, ... from this call), whichever call runs it,
         folds the state of every chain into one running mean field and one M2 field in HBM
         (mgmc_field_stats_enable; the Welford update of qoi_moments, chains in order).  On a sampler
         that already records: a reset with the new stride.
         batch=B: also the batch means of B recorded cycles each, pooled over the chains
-        (mgmc_field_stats_enable_batched), for field_mean_stderr and field_iact."""
-        if batch is None:
+        (mgmc_field_stats_enable_batched), for field_mean_stderr and field_iact.
+        conditional=True: the Rao-Blackwellised statistics (mgmc_field_stats_enable_cond): the fields fold
+        c = x + D^-1 (f - Q x), the conditional mean of every vertex given the rest, in place of x;
+        field_rb_mean_variance then gives the estimates, field_mean_stderr and field_iact describe c.
+        two_pass=True takes the two-pass path where the plan would fuse.  set_lowrank resets them."""
+        if conditional:
+            self._chk(self.lib.mgmc_field_stats_enable_cond(self.handle, int(stride), 0 if batch is None else int(batch),
+                                                            1 if two_pass else 0))
+        elif two_pass:
+            raise ValueError("two_pass applies to conditional=True")
+        elif batch is None:
             self._chk(self.lib.mgmc_field_stats_enable(self.handle, int(stride)))
         else:
             self._chk(self.lib.mgmc_field_stats_enable_batched(self.handle, int(stride), int(batch)))
@@ -645,6 +666,27 @@ class MultigridMCSampler:
         if n == 0:
             raise ValueError("no state has been recorded yet")
         return mean, m2 / n
+
+    def field_cond_info(self) -> dict:
+        """{"enabled": bool, "path": "fused" | "two_pass" | None}: the Rao-Blackwellised mode and its kernels"""
+        en, path = ctypes.c_int(), ctypes.c_int()
+        self._chk(self.lib.mgmc_field_stats_cond_info(self.handle, ctypes.byref(en), ctypes.byref(path)))
+        return {"enabled": bool(en.value), "path": {1: "fused", 2: "two_pass"}.get(path.value)}
+
+    def field_conditional_precision(self):
+        """d = diag(Q) as the Rao-Blackwellised statistics use it (reference layout): 1 / d is the conditional
+        variance of a vertex given the rest.  Only in conditional mode."""
+        d = np.empty(self.ndof)
+        self._chk(self.lib.mgmc_field_stats_get_cond_precision(self.handle, _dp(d), self.ndof))
+        return d
+
+    def field_rb_mean_variance(self):
+        """(mean, variance): the Rao-Blackwell estimates of the posterior mean and the marginal variance per
+        vertex (rao_blackwell_estimates).  ValueError in plain mode or before the first recorded state."""
+        if not self.field_cond_info()["enabled"]:
+            raise ValueError("the Rao-Blackwellised statistics are not enabled (field_stats(conditional=True))")
+        n, mean, m2 = self.field_moments()
+        return rao_blackwell_estimates(n, mean, m2, self.field_conditional_precision())
 
     def field_batch_info(self) -> dict:
         """{"batch": batch length in recorded cycles (0 without batching or while disabled),
@@ -976,4 +1018,5 @@ __all__ = [
     "HipMulticolourSORSmoother", "SORSmoother", "SSORSmoother", "SORSmootherFactory", "SSORSmootherFactory", "measurement_vector_index", "ConstantCorrelationLengthModel",
     "PeriodicCorrelationLengthModel", "SquaredShiftedLaplaceFDOperator", "comm_unique_id", "make_config", "describe", "FORWARD", "BACKWARD",
     "batch_means_estimates",
+    "rao_blackwell_estimates",
 ]
