@@ -436,6 +436,53 @@ int mgmc_energy_get_series(mgmc_handle* h, int chain, double* xqx, double* fx, s
 int mgmc_energy_moments(mgmc_handle* h, int chain, double out[3]);
                                                           /* (n, mean, M2) of E = xqx - 2 fx */
 
+/* ---- QoI panel: K linear functionals z_k = b_k^T x per cycle and their joint statistics, on the device ----
+ * The reference's Statistics (src/auxilliary/statistics.hh, statistics.cc) for a vector-valued observable: the
+ * running average and covariance (statistics.cc:5-18, :41-51), the autocovariance over a window (:19-38, :54-62)
+ * and from it tau_int (:65-80).  The natural panel of a posterior run is the predicted data B^T x at the
+ * measurement sites plus the driver's QoI.
+ * A panel is K <= 64 columns in CSC form, mgmc_set_lowrank's format: colptr[K + 1], rows = reference vertex
+ * indices strictly ascending per column, vals.  A column that lists all N vertices is a dense column: dense
+ * columns are read in groups that load each x once, and one whose values are all the same bits needs no value
+ * array.  Column k is summed in mgmc_set_qoi_vector's order (4096-entry blocks, lane-strided, xor butterfly;
+ * DESIGN.md section 3l), so it equals bit for bit what MGMC_QOI_VECTOR records for that vector.  K = 0 removes
+ * the panel (and ends its recording).  mgmc_qoi_panel_set on a recording handle starts the records again.
+ * mgmc_set_lowrank, mgmc_set_rhs, mgmc_set_state, mgmc_set_qoi_vector and mgmc_reset_moments do not touch the
+ * panel or its records; the scalar QoI (series, moments) keeps its bits whether or not a panel records.
+ * MGMC_E_INVALID (handle and installed panel unchanged): K outside [0, 64], colptr[0] != 0 or decreasing, an
+ * empty column, rows out of range or not strictly ascending, a non-finite value.  MGMC_E_NOMEM: likewise unchanged.
+ * A HIP failure while a recording handle takes its new panel leaves the new panel installed and the recording
+ * off (the cycle without the op), as a failed mgmc_qoi_panel_record_enable does. */
+int mgmc_qoi_panel_set(mgmc_handle* h, int K, const int64_t* colptr, const int64_t* rows, const double* vals);
+int mgmc_qoi_panel_eval(mgmc_handle* h, double* out);     /* out[chain * K + k] = b_k^T x of the current state;
+                                                             nothing is recorded */
+/* Recording: while enabled, every stride-th cycle (numbered 1, 2, ... from the enable / reset on) records z of
+ * every chain from an op right after the QoI record: the series keeps the first `capacity` records; the mean and
+ * the co-moments C (cnt = n + 1; delta_k = z_k - mean_k; mean_k += delta_k / cnt; C[k][l] += delta_k (z_l -
+ * mean_l), all deltas from the old means, all means updated first: the diagonal is mgmc_qoi_moments' M2 update)
+ * and, per column, S[j] for lags j < window, 1 <= window <= 256 (statistics.cc:19-38: N_j = records - j,
+ * S[j] = z_now z_lag if N_j == 1, else S[j] += (z_now z_lag - S[j]) / N_j) keep counting.  Disabled (the default)
+ * the cycle and its graphs are those of a handle without a panel.  MGMC_E_INVALID: no panel installed, stride < 1,
+ * window outside [1, 256], capacity < 1, a chain out of range, get_series / moments / autocov / reset while
+ * disabled, n beyond the records kept; MGMC_E_NOMEM leaves the handle as it was. */
+int mgmc_qoi_panel_record_enable(mgmc_handle* h, int stride, int window, int64_t capacity);
+                                                          /* allocates + zeroes, rebuilds graphs; on an enabled handle
+                                                             with the same window and capacity: a reset */
+int mgmc_qoi_panel_record_disable(mgmc_handle* h);        /* frees, rebuilds graphs; no-op when disabled */
+int mgmc_qoi_panel_record_reset(mgmc_handle* h);          /* zero moments, S and the counters; no graph rebuild */
+int mgmc_qoi_panel_info(const mgmc_handle* h, int* K, int* enabled, int* stride, int* window, uint64_t* ncycles,
+                        uint64_t* nrecorded);
+int mgmc_qoi_panel_get_series(mgmc_handle* h, int chain, double* out, size_t n);
+                                                          /* out[r * K + k], the first n records,
+                                                             n <= min(nrecorded, capacity) */
+int mgmc_qoi_panel_moments(mgmc_handle* h, int chain, double* count, double* mean, double* comoment);
+                                                          /* mean[K]; comoment[K * K] = C, the upper triangle the
+                                                             device keeps mirrored; the reference's covariance()
+                                                             (statistics.cc:41-45) is C / (count - 1) */
+int mgmc_qoi_panel_autocov(mgmc_handle* h, int chain, double* S, int* nlags);
+                                                          /* S[k * window + j]; *nlags = min(window, nrecorded)
+                                                             lags hold values; C_k(j) = S[k][j] - mean_k^2 */
+
 /* ---- component entry points (host buffers, reference layout) used by the parity tests ---- */
 /* y = Q_level x  (LinearOperator::apply; Q = A + B Sigma^{-1} B^T once mgmc_set_lowrank ran) */
 int mgmc_operator_apply(mgmc_handle* h, int level, const double* x, double* y);

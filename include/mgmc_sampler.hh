@@ -212,6 +212,51 @@ class HipMultigridMCSampler {
     void energy_moments(int chain, double out[3]) const {
         check(mgmc_energy_moments(h_.get(), chain, out), h_.get(), "mgmc_energy_moments");
     }
+    // QoI panel (mgmc_qoi_panel_*; the reference's Statistics, auxilliary/statistics.hh): K <= 64 functionals
+    // b_k^T x in CSC form (rows strictly ascending per column, a column of all vertices is dense); K = 0 removes
+    void set_qoi_panel(int K, const int64_t* colptr, const int64_t* rows, const double* vals) {
+        check(mgmc_qoi_panel_set(h_.get(), K, colptr, rows, vals), h_.get(), "mgmc_qoi_panel_set");
+    }
+    int qoi_panel_size() const {
+        int K = 0;
+        check(mgmc_qoi_panel_info(h_.get(), &K, nullptr, nullptr, nullptr, nullptr, nullptr), h_.get(),
+              "mgmc_qoi_panel_info");
+        return K;
+    }
+    // z of the current state, nchains() x K; nothing recorded
+    std::vector<double> qoi_panel_eval() const {
+        std::vector<double> z((size_t)nchains() * (size_t)qoi_panel_size());
+        check(mgmc_qoi_panel_eval(h_.get(), z.data()), h_.get(), "mgmc_qoi_panel_eval");
+        return z;
+    }
+    // every stride-th cycle from here on records z per chain: the first `capacity` records, mean, co-moments and
+    // the autocovariance over `window` lags (Statistics::record_sample, statistics.cc:5-38)
+    void qoi_panel_record(int stride = 1, int window = 32, int64_t capacity = 4096) {
+        check(mgmc_qoi_panel_record_enable(h_.get(), stride, window, capacity), h_.get(), "mgmc_qoi_panel_record_enable");
+    }
+    void qoi_panel_off() { check(mgmc_qoi_panel_record_disable(h_.get()), h_.get(), "mgmc_qoi_panel_record_disable"); }
+    void reset_qoi_panel() { check(mgmc_qoi_panel_record_reset(h_.get()), h_.get(), "mgmc_qoi_panel_record_reset"); }
+    // cycles recorded since the enable / reset; 0 while disabled
+    uint64_t qoi_panel_recorded() const {
+        uint64_t n = 0;
+        check(mgmc_qoi_panel_info(h_.get(), nullptr, nullptr, nullptr, nullptr, nullptr, &n), h_.get(),
+              "mgmc_qoi_panel_info");
+        return n;
+    }
+    // the first n records of one chain, out[r * K + k]
+    void qoi_panel_series(int chain, double* out, size_t n) const {
+        check(mgmc_qoi_panel_get_series(h_.get(), chain, out, n), h_.get(), "mgmc_qoi_panel_get_series");
+    }
+    // count, mean[K] and the co-moments C[K * K] of one chain; Statistics::covariance() is C / (count - 1)
+    void qoi_panel_moments(int chain, double* count, double* mean, double* comoment) const {
+        check(mgmc_qoi_panel_moments(h_.get(), chain, count, mean, comoment), h_.get(), "mgmc_qoi_panel_moments");
+    }
+    // S[k * window + j], the lags j < the returned count hold values; C_k(j) = S - mean_k^2 (statistics.cc:54-62)
+    int qoi_panel_autocovariance(int chain, double* S) const {
+        int nlags = 0;
+        check(mgmc_qoi_panel_autocov(h_.get(), chain, S, &nlags), h_.get(), "mgmc_qoi_panel_autocov");
+        return nlags;
+    }
 
    private:
     void adopt(mgmc_handle* h) {

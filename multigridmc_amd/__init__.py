@@ -6,7 +6,13 @@ csrc/*.hip behind the C-ABI of include/mgmc.h; this package is the host-side mir
 reference's Sampler / LinearOperator interfaces.
 """
 from ._native import QOI_VECTOR, MgmcError, load_library  # noqa: F401
-from .measured import LowRankUpdate, MeasuredOperator, measurement_vector, synthetic_posterior  # noqa: F401
+from .measured import (  # noqa: F401
+    LowRankUpdate,
+    MeasuredOperator,
+    measurement_panel,
+    measurement_vector,
+    synthetic_posterior,
+)
 from .parameters import MultigridParameters, read_config  # noqa: F401
 from .sampler import (  # noqa: F401
     BACKWARD,
@@ -26,7 +32,10 @@ from .sampler import (  # noqa: F401
     SSORSmootherFactory,
     ConstantCorrelationLengthModel,
     PeriodicCorrelationLengthModel,
+    PanelStatistics,
     batch_means_estimates,
+    panel_statistics,
+    tau_int_from_autocov,
     rao_blackwell_estimates,
     comm_unique_id,
     csr_colour_scheme,

@@ -140,6 +140,16 @@ SIGNATURES = [
     ("mgmc_energy_record_info", c_int, [_H, POINTER(c_int), POINTER(c_int), POINTER(c_uint64), POINTER(c_uint64)]),
     ("mgmc_energy_get_series", c_int, [_H, c_int, _DP, _DP, c_size_t]),
     ("mgmc_energy_moments", c_int, [_H, c_int, _DP]),
+    ("mgmc_qoi_panel_set", c_int, [_H, c_int, POINTER(c_int64), POINTER(c_int64), _DP]),
+    ("mgmc_qoi_panel_eval", c_int, [_H, _DP]),
+    ("mgmc_qoi_panel_record_enable", c_int, [_H, c_int, c_int, c_int64]),
+    ("mgmc_qoi_panel_record_disable", c_int, [_H]),
+    ("mgmc_qoi_panel_record_reset", c_int, [_H]),
+    ("mgmc_qoi_panel_info", c_int, [_H, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int),
+                                    POINTER(c_uint64), POINTER(c_uint64)]),
+    ("mgmc_qoi_panel_get_series", c_int, [_H, c_int, _DP, c_size_t]),
+    ("mgmc_qoi_panel_moments", c_int, [_H, c_int, _DP, _DP, _DP]),
+    ("mgmc_qoi_panel_autocov", c_int, [_H, c_int, _DP, POINTER(c_int)]),
     ("mgmc_operator_apply", c_int, [_H, c_int, _DP, _DP]),
     ("mgmc_smoother_apply", c_int, [_H, c_int, c_int, c_int, _DP, _DP]),
     ("mgmc_sor_smoother_apply", c_int, [_H, c_int, c_int, c_int, _DP, _DP]),

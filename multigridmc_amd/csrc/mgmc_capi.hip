@@ -1765,9 +1765,13 @@ int build_tails(mgmc_handle* h) {
 // The field-statistics op is the last op of the cycle, after OP_QOI, while the statistics are enabled and
 // absent otherwise: appended once the passes above have run (none of them sees it), so the rest of the
 // op list is what it is without the statistics.  It lies behind seg_end_post: in the timed graph's last
-// (QoI) segment.  The energy op (mgmc_energy_record_enable) likewise, between OP_QOI and OP_FIELDSTATS.
+// (QoI) segment.  The energy op (mgmc_energy_record_enable) likewise, between OP_QOI and OP_FIELDSTATS, and the
+// QoI panel's (mgmc_qoi_panel_record_enable) right after OP_QOI.
 void sync_fieldstats_op(mgmc_handle* h) {
-    while (!h->ops.empty() && (h->ops.back().kind == OP_FIELDSTATS || h->ops.back().kind == OP_ENERGY)) h->ops.pop_back();
+    while (!h->ops.empty() && (h->ops.back().kind == OP_FIELDSTATS || h->ops.back().kind == OP_ENERGY ||
+                               h->ops.back().kind == OP_PANEL))
+        h->ops.pop_back();
+    if (h->qp_ctl && !h->ops.empty()) h->ops.push_back({OP_PANEL, 0, 0, 0, 0});
     if (h->en_ctl && !h->ops.empty()) h->ops.push_back({OP_ENERGY, 0, 0, 0, 0});
     if (h->fs_mean && !h->ops.empty()) h->ops.push_back({OP_FIELDSTATS, 0, 0, 0, 0});
 }
@@ -2056,6 +2060,10 @@ void enqueue_ops(mgmc_handle* h, size_t begin, size_t end, hipStream_t s) {
                 hipLaunchKernelGGL(k_qoi_record, dim3(1), dim3(64 * ((nch + 63) / 64)), 0, s,
                                    (const double*)h->levels[0].x, h->ctrl, h->series, h->series_cap, h->mom, nch,
                                    (long long)h->levels[0].L.nstore);
+                break;
+            }
+            case OP_PANEL: {  // (level 0's canonical buffer, as below)
+                launch_panel(h, h->qp_ctl, s);
                 break;
             }
             case OP_ENERGY: {  // (level 0's canonical buffer, as below)
@@ -2856,6 +2864,12 @@ int mgmc_destroy(mgmc_handle* h) {
     if (h->en_sq) hipFree(h->en_sq);
     if (h->en_sf) hipFree(h->en_sf);
     if (h->en_mom) hipFree(h->en_mom);
+    for (void* p : h->qp_allocs) hipFree(p);
+    if (h->qp_ctl) hipFree(h->qp_ctl);
+    if (h->qp_series) hipFree(h->qp_series);
+    if (h->qp_mom) hipFree(h->qp_mom);
+    if (h->qp_ring) hipFree(h->qp_ring);
+    if (h->qp_S) hipFree(h->qp_S);
     if (h->stream) hipStreamDestroy(h->stream);
     delete h;
     return MGMC_OK;

@@ -9,6 +9,7 @@
 //   mgmc_solve.hip         the exact-statistics engine (mgmc_solve)
 //   mgmc_lowrank_setup.hip the low-rank posterior part (mgmc_set_lowrank)
 //   mgmc_comm.hip          the RCCL communicator (mgmc_comm_*)
+//   mgmc_panel.hip         the QoI panel (mgmc_qoi_panel_*, mgmc_panel.hpp)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -52,6 +53,11 @@ static_assert(MGMC_LAYOUT_POINT == mgmc::LF_POINT && MGMC_LAYOUT_PAIRS == mgmc::
 #include "mgmc_fieldcond.hpp"
 #include "mgmc_fieldcond_host.hpp"
 
+namespace mgmc {
+struct PanelWork;    // mgmc_panel.hpp (included by mgmc_panel.hip only)
+struct PanelColumn;
+}  // namespace mgmc
+
 using namespace mgmc;
 
 namespace mgmc_host {
@@ -71,8 +77,10 @@ enum OpKind {
     OP_SWEEP_RESTRICT = 8,  // 2D Galerkin level: last pre-sweep + residual + restriction (mgmc_qrestrict.hpp)
     OP_FIELDSTATS = 9,      // pointwise mean / M2 of the level-0 state (mgmc_fieldstats.hpp); the last op, only
                             // while mgmc_field_stats_enable holds
-    OP_ENERGY = 10          // x^T Q x and f^T x of the level-0 state (mgmc_energy.hpp); after OP_QOI and before
+    OP_ENERGY = 10,         // x^T Q x and f^T x of the level-0 state (mgmc_energy.hpp); after OP_QOI and before
                             // OP_FIELDSTATS, only while mgmc_energy_record_enable holds
+    OP_PANEL = 11           // the QoI panel's K dots and their statistics (mgmc_panel.hpp); right after OP_QOI, only
+                            // while mgmc_qoi_panel_record_enable holds
 };
 
 struct Op {
@@ -289,6 +297,25 @@ struct mgmc_handle {
     double* en_mom = nullptr;       // (n, mean, M2, pad) of E = xqx - 2 fx per chain
     int en_stride = 0;
     uint64_t en_cap = 0;
+    // QoI panel (mgmc_qoi_panel_*, mgmc_panel.hpp): installed <=> qp_K > 0; one allocation list, freed together
+    int qp_K = 0;
+    int qp_nwork = 0, qp_nslot = 0;  // wavefronts of k_panel_dots; block partials per chain
+    PanelWork* qp_work = nullptr;
+    PanelColumn* qp_col = nullptr;
+    long long* qp_ent_off = nullptr;  // entry-list columns: padded offsets, values
+    double* qp_ent_val = nullptr;
+    double* qp_dense_val = nullptr;   // dense columns with distinct values, reference order
+    double* qp_part = nullptr;        // [chain][qp_nslot]
+    double* qp_out = nullptr;         // [chain][K] (mgmc_qoi_panel_eval)
+    std::vector<void*> qp_allocs;
+    // ... recording (mgmc_qoi_panel_record_*): enabled <=> qp_ctl != nullptr
+    uint64_t* qp_ctl = nullptr;     // [chain][QP_CTL_WORDS] (mgmc_panel.hpp)
+    double* qp_series = nullptr;    // [chain][capacity][K]
+    double* qp_mom = nullptr;       // [chain][1 + K + K * K]
+    double* qp_ring = nullptr;      // [chain][window][K]
+    double* qp_S = nullptr;         // [chain][K][window]
+    int qp_stride = 0, qp_window = 0;
+    uint64_t qp_cap = 0;
     std::string last_error;
     ncclComm_t comm = nullptr;
     int nranks = 1, rank = 0;
@@ -401,6 +428,7 @@ Layout tail_layout(const Layout& L);
 void build_ops(mgmc_handle* h);
 int build_tails(mgmc_handle* h);
 void sync_fieldstats_op(mgmc_handle* h);
+void launch_panel(mgmc_handle* h, uint64_t* ctl, hipStream_t s);  // mgmc_panel.hip
 int fieldcond_lowrank_changed(mgmc_handle* h);
 bool mark_rhs_zero(mgmc_handle* h);
 int build_graphs(mgmc_handle* h);

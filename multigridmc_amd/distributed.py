@@ -29,6 +29,37 @@ def merge_moments(parts) -> tuple:
     return n, mean, m2
 
 
+def merge_panel_moments(parts) -> tuple:
+    """The matrix form of merge_moments for a vector observable (the QoI panel): [(n, mean[K], C[K, K]), ...] in
+    the given order, C = sum (z - mean)(z - mean)^T:
+        mean <- mean + delta nb / tot,   C <- C + Cb + delta delta^T n nb / tot,   delta = mean_b - mean."""
+    n, mean, C = 0.0, None, None
+    for nb, mb, Cb in parts:
+        nb = float(nb)
+        if nb == 0:
+            continue
+        mb, Cb = np.asarray(mb, dtype=np.float64), np.asarray(Cb, dtype=np.float64)
+        if n == 0:
+            n, mean, C = nb, mb.copy(), Cb.copy()
+            continue
+        tot = n + nb
+        delta = mb - mean
+        mean = mean + delta * nb / tot
+        C = C + Cb + np.outer(delta, delta) * n * nb / tot
+        n = tot
+    if mean is None:
+        raise ValueError("merge_panel_moments: no samples")
+    return n, mean, C
+
+
+def panel_moments_of(series) -> tuple:
+    """(n, mean, C) of an (n, K) series, two-pass"""
+    s = np.asarray(series, dtype=np.float64)
+    mean = s.mean(axis=0)
+    d = s - mean
+    return float(s.shape[0]), mean, d.T @ d
+
+
 def moments_of(series) -> tuple:
     s = np.asarray(series, dtype=np.float64)
     if s.size == 0:

@@ -8,6 +8,9 @@ Mirrors the Multigrid MC part of the reference's driver (src/driver_mgmc.cc):
     observed mean and variance ......................................................... :40-107
     (--energy-stride S: also the whole-field energy x^T Q x, f^T x of every S-th of those samples, reduced
     on the device, to energy_multigridmc.txt, and the chi-square check of its mean; not in the reference)
+    (--qoi-panel: also the QoI panel -- the predicted data B^T x at every measurement site and the QoI vector as
+    the last column -- recorded on the device with its covariance and tau_int, printed in the layout of the
+    reference's Statistics, auxilliary/statistics.cc:88-108, and written to panel_multigridmc.txt)
   * measure_convergence: nsamplesconvergence chains from x = 0, nstepsconvergence cycles
     each; |E[z^k] - E[z]| and |Var[z^k] - Var[z]| with error bars to
     convergence_multigridmc.txt ........................................................ :188-314
@@ -36,7 +39,7 @@ import time
 import numpy as np
 
 from . import _native as mg_native
-from .measured import MeasuredOperator, measurement_vector
+from .measured import MeasuredOperator, measurement_panel, measurement_vector
 from .parameters import (ConfigError, ConstantCorrelationLengthModelParameters, GeneralParameters,
                          LatticeParameters, MeasurementFileError, MeasurementParameters, MultigridParameters,
                          PeriodicCorrelationLengthModelParameters, PriorParameters, SamplingParameters, read_config)
@@ -135,11 +138,56 @@ def report_energy(sampler, label: str, f, mean_x_exact, filename: str = "energy_
     return float(e.mean()), N, float(z)
 
 
+PANEL_WINDOW = 32      # autocorrelation window of --qoi-panel
+PANEL_EXACT_MAX_K = 16  # the exact mean and covariance take K solves
+
+
+def report_panel(sampler, label: str, exact: ExactTargets, columns, mean_x_exact,
+                 filename: str = "panel_multigridmc.txt"):
+    """The recorded QoI panel (MultigridMCSampler.qoi_panel_record) in the layout of the reference's
+    operator<<(Statistics) (statistics.cc:88-108): Avg, Var, tau_{int,j} per column, window, # samples; the
+    records (cycle, z_0 .. z_{K-1}) go to `filename`.  With at most PANEL_EXACT_MAX_K columns also the exact mean
+    b_k^T Q^-1 f = b_k^T mean_x_exact and covariance b_k^T Q^-1 b_l (one solve per column)."""
+    info = sampler.qoi_panel_info()
+    z = sampler.qoi_panel_series(0)
+    with open(filename, "w") as out:
+        for r in range(len(z)):
+            out.write(f"{(r + 1) * info['stride']:d} " + " ".join(f"{v:.17g}" for v in z[r]) + "\n")
+    n, mean, cov = sampler.qoi_panel_moments(0)
+    tau = sampler.qoi_panel_tau_int(0)
+    K = info["K"]
+
+    def vec(v):
+        return " ".join(f"{x:.6f}" for x in v)
+
+    def mat(m):
+        return "\n".join(("" if r == 0 else " " * (len(label) + 9)) + vec(m[r]) for r in range(len(m)))
+
+    print(f" {label}: Avg = {vec(mean)}")
+    print(f" {label}: Var = {mat(cov)}")
+    for j in range(K):
+        print(f" {label}: tau_{{int,j}} = {tau[j]:.3f}")
+    print(f" {label}: window      = {info['window']}")
+    print(f" {label}: # samples   = {int(n)}")
+    if K > PANEL_EXACT_MAX_K:
+        print(f" {'exact'}: skipped, the exact mean and covariance of {K} > {PANEL_EXACT_MAX_K} columns take {K} solves\n")
+        return mean, cov, tau, None, None
+    B = np.zeros((sampler.ndof, K))
+    for k, (rows, vals) in enumerate(columns):
+        B[rows, k] = vals
+    U = np.stack([exact.solve(B[:, k]) for k in range(K)], axis=1)
+    mean_exact, cov_exact = B.T @ mean_x_exact, B.T @ U
+    print(f" {'exact'}: Avg = {vec(mean_exact)}")
+    print(f" {'exact'}: Var = {mat(cov_exact)}\n")
+    return mean, cov, tau, mean_exact, cov_exact
+
+
 def measure_sampling_time(sampler, exact: ExactTargets, sampling_params: SamplingParameters,
                           measurement_params: MeasurementParameters, label: str, filename: str,
-                          energy_stride=None):
+                          energy_stride=None, qoi_panel=None):
     """driver_mgmc.cc:40-107.  energy_stride=S (--energy-stride S): the energy of every S-th sample is recorded on
-    the device (report_energy)."""
+    the device (report_energy).  qoi_panel (--qoi-panel): the measured operator whose columns, with the QoI vector
+    as the last one, are recorded as a panel (report_panel)."""
     op = sampler.get_linear_operator()
     y = _measured_values(measurement_params)
     mean_x_exact = exact.posterior_mean(y) if op.get_m_lowrank() > 0 else np.zeros(op.get_ndof())
@@ -150,6 +198,11 @@ def measure_sampling_time(sampler, exact: ExactTargets, sampling_params: Samplin
     _qoi_series(sampler, sampling_params.nwarmup, rows, vals)
     if energy_stride is not None:
         sampler.energy_record(energy_stride, max(1, sampling_params.nsamples // energy_stride))
+    panel_columns = None
+    if qoi_panel is not None:
+        panel_columns = measurement_panel(qoi_panel, extra=[(rows, vals)])
+        sampler.set_qoi_panel(panel_columns)
+        sampler.qoi_panel_record(1, PANEL_WINDOW, max(1, sampling_params.nsamples))
     t0 = time.perf_counter()
     data = _qoi_series(sampler, sampling_params.nsamples, rows, vals)
     t_elapsed = (time.perf_counter() - t0) * 1e3 / sampling_params.nsamples
@@ -159,6 +212,11 @@ def measure_sampling_time(sampler, exact: ExactTargets, sampling_params: Samplin
             report_energy(sampler, label, f, mean_x_exact)
         finally:
             sampler.energy_record_off()
+    if panel_columns is not None:
+        try:
+            report_panel(sampler, label, exact, panel_columns, mean_x_exact)
+        finally:
+            sampler.set_qoi_panel(None)
     with open(filename, "w") as out:
         for v in data:
             out.write(f"{v:g}\n")
@@ -301,10 +359,15 @@ def main(argv=None) -> int:
     stderr_batch = None
     energy_stride = None
     rao_blackwell = False
+    qoi_panel = False
     while (len(argv) >= 3 and argv[0] in ("--convergence-batch", "--stderr-batch", "--energy-stride")) or \
-            (len(argv) >= 2 and argv[0] == "--rao-blackwell"):
+            (len(argv) >= 2 and argv[0] in ("--rao-blackwell", "--qoi-panel")):
         if argv[0] == "--rao-blackwell":  # posterior_statistics: the Rao-Blackwell estimates of mean and variance
             rao_blackwell = True
+            argv = argv[1:]
+            continue
+        if argv[0] == "--qoi-panel":  # measure_sampling_time: the predicted data and the QoI as a panel
+            qoi_panel = True
             argv = argv[1:]
             continue
         if argv[0] == "--convergence-batch":  # concurrent measure_convergence chains
@@ -316,7 +379,7 @@ def main(argv=None) -> int:
         argv = argv[2:]
     if len(argv) != 1:
         print(f"Usage: {sys.argv[0]} [--convergence-batch N] [--stderr-batch B] [--energy-stride S] "
-              "[--rao-blackwell] CONFIGURATIONFILE")
+              "[--rao-blackwell] [--qoi-panel] CONFIGURATIONFILE")
         return -1
     t_start = time.time()
     print("\n+--------------------------------+")
@@ -389,7 +452,7 @@ def main(argv=None) -> int:
     if general.do_multigridmc:
         print("**** Multigrid MC ****")
         measure_sampling_time(sampler, exact, sampling_params, measurement_params, "MGMC",
-                              "timeseries_multigridmc.txt", energy_stride)
+                              "timeseries_multigridmc.txt", energy_stride, posterior if qoi_panel else None)
         measure_convergence(sampler, exact, sampling_params, measurement_params, "convergence_multigridmc.txt",
                             batch)
         if general.save_posterior_statistics:

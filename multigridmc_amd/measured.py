@@ -204,7 +204,20 @@ class MeasuredOperator:
         return measurement_vector(self.lattice, x0, radius)
 
 
-__all__ = ["V_sphere", "gauss_legendre_order1", "measurement_vector", "LowRankUpdate", "MeasuredOperator"]
+def measurement_panel(measured_operator, extra=()):
+    """The QoI panel of a posterior run (MultigridMCSampler.set_qoi_panel): the columns of B in order -- the
+    predicted data B^T x at the measurement sites, the global-average column included when the operator has one
+    -- followed by the `extra` (rows, vals) vectors.  A list of (rows, vals) pairs."""
+    lr = measured_operator.get_B()
+    cols = [(lr.rows[lr.colptr[k]:lr.colptr[k + 1]].copy(), lr.vals[lr.colptr[k]:lr.colptr[k + 1]].copy())
+            for k in range(lr.m)]
+    for r, v in extra:
+        cols.append((np.ascontiguousarray(r, dtype=np.int64), np.ascontiguousarray(v, dtype=np.float64)))
+    return cols
+
+
+__all__ = ["V_sphere", "gauss_legendre_order1", "measurement_vector", "LowRankUpdate", "MeasuredOperator",
+           "measurement_panel"]
 
 
 def synthetic_posterior(prior, m: int, radius: float = 0.0, measure_global: bool = False,

@@ -396,6 +396,98 @@ def rao_blackwell_estimates(n, mean, m2, d):
     return mean, 1.0 / np.asarray(d, dtype=np.float64) + m2 / n
 
 
+def tau_int_from_autocov(C):
+    """tau_int per row of C[k, j], the autocovariance of observable k at lags j = 0 .. L - 1 (statistics.cc:65-80):
+    1 + 2 sum_{j=1}^{L-1} (1 - j / L) C[k, j] / C[k, 0]."""
+    C = np.atleast_2d(np.asarray(C, dtype=np.float64))
+    L = C.shape[1]
+    tau = np.ones(C.shape[0])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for j in range(1, L):
+            tau = tau + 2 * (1.0 - j / (1.0 * L)) * C[:, j] / C[:, 0]
+    return tau
+
+
+class PanelStatistics:
+    """The reference's Statistics (src/auxilliary/statistics.hh, statistics.cc) restated for a host series of a
+    vector-valued observable: record_sample's running averages avg, avg2 and S_j over a window of lags
+    (statistics.cc:5-38), average(), covariance() = n / (n - 1) (avg2 - avg avg^T) (:41-51), auto_covariance():
+    C(j) = S_j - avg avg^T (:54-62), tau_int(v) (:65-80).  The arithmetic keeps the reference's operand order."""
+
+    def __init__(self, dim: int, window: int):
+        if window < 1:
+            raise ValueError("window must be >= 1")
+        self.dim, self.window = int(dim), int(window)
+        self.reset()
+
+    def reset(self):
+        self.n_samples = 0
+        self.avg = np.zeros(self.dim)
+        self.avg2 = np.zeros((self.dim, self.dim))
+        self._Q = np.zeros((self.window, self.dim))  # ring: record i lives in slot i % window
+        self.S = np.zeros((0, self.dim, self.dim))   # S_0 .. S_{L-1}
+
+    def record_sample(self, Q):
+        Q = np.asarray(Q, dtype=np.float64).reshape(self.dim)
+        i = self.n_samples
+        self.n_samples = n = i + 1
+        if n == 1:
+            self.avg = Q.copy()
+            self.avg2 = np.outer(Q, Q)
+        else:
+            self.avg = self.avg + (Q - self.avg) / (1.0 * n)
+            self.avg2 = self.avg2 + (np.outer(Q, Q) - self.avg2) / (1.0 * n)
+        self._Q[i % self.window] = Q
+        L = min(self.window, n)
+        lagged = self._Q[(i - np.arange(L)) % self.window]          # Q_k[0], Q_k[1], ...
+        prod = Q[None, :, None] * lagged[:, None, :]                # Q_k[0] Q_k[j]^T
+        if L > len(self.S):                                         # N_j == 1: push_back
+            self.S = np.concatenate([self.S, prod[len(self.S):]])
+            upd = L - 1
+        else:
+            upd = L
+        if upd:
+            Nj = (n - np.arange(upd)).astype(np.float64)[:, None, None]
+            self.S[:upd] = self.S[:upd] + (prod[:upd] - self.S[:upd]) / (1.0 * Nj)
+
+    def samples(self) -> int:
+        return self.n_samples
+
+    def average(self):
+        return self.avg.copy()
+
+    def covariance(self):
+        n = np.float64(self.n_samples)  # (one sample: inf * 0 = nan, the reference's 1 / 0.0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return 1.0 * n / (n - 1.0) * (self.avg2 - np.outer(self.avg, self.avg))
+
+    def auto_covariance(self):
+        """C(j), j = 0 .. L - 1: an (L, dim, dim) array, L = min(window, samples) stored lags"""
+        return self.S - np.outer(self.avg, self.avg)[None]
+
+    def tau_int(self, v) -> float:
+        v = np.asarray(v, dtype=np.float64).reshape(self.dim)
+        C = self.auto_covariance()
+        return float(tau_int_from_autocov(np.einsum("a,jab,b->j", v, C, v)[None])[0])
+
+    def tau_int_columns(self):
+        """tau_int of every unit direction (what operator<< prints, statistics.cc:95-102)"""
+        C = self.auto_covariance()
+        return tau_int_from_autocov(np.einsum("jkk->kj", C))
+
+
+def panel_statistics(series, window: int) -> PanelStatistics:
+    """The reference's Statistics of a host series: series[i] is sample i of a K-vector observable ((n, K); a 1D
+    series is one observable), window the number of lags kept (autocorr_window)."""
+    s = np.asarray(series, dtype=np.float64)
+    if s.ndim == 1:
+        s = s[:, None]
+    st = PanelStatistics(s.shape[1], window)
+    for q in s:
+        st.record_sample(q)
+    return st
+
+
 class MultigridMCSampler:
     """Device MGMC sampler with the reference's Sampler interface (sampler/sampler.hh:23-72).
 
@@ -767,6 +859,120 @@ class MultigridMCSampler:
         out = np.zeros(3)
         self._chk(self.lib.mgmc_energy_moments(self.handle, int(chain), _dp(out)))
         return out
+
+    # -- QoI panel: K functionals b_k^T x per cycle and their joint statistics (mgmc_qoi_panel_*, DESIGN.md 3l;
+    #    the reference's Statistics, src/auxilliary/statistics.{hh,cc}) --
+    def set_qoi_panel(self, columns):
+        """Install the panel: a list of (rows, vals) pairs (rows strictly ascending vertex indices; a column
+        listing every vertex is a dense column) or a scipy sparse matrix with ndof rows, one functional per
+        column.  At most 64 columns; an empty list (or None) removes the panel.  Column k is summed in
+        set_qoi_vector's order: it records what sample(..., QOI_VECTOR) records for that vector, bit for bit.
+        On a recording sampler the records start again."""
+        P = ctypes.POINTER(ctypes.c_int64)
+        if columns is None or (not hasattr(columns, "tocsc") and len(columns) == 0):
+            self._chk(self.lib.mgmc_qoi_panel_set(self.handle, 0, None, None, None))
+            return
+        if hasattr(columns, "tocsc"):
+            m = columns.tocsc()
+            if m.shape[0] != self.ndof:
+                raise ValueError(f"the panel matrix has {m.shape[0]} rows, the operator {self.ndof}")
+            m.sort_indices()
+            colptr = np.ascontiguousarray(m.indptr, dtype=np.int64)
+            rows = np.ascontiguousarray(m.indices, dtype=np.int64)
+            vals = np.ascontiguousarray(m.data, dtype=np.float64)
+        else:
+            cols = [(np.ascontiguousarray(r, dtype=np.int64).ravel(), np.ascontiguousarray(v, dtype=np.float64).ravel())
+                    for r, v in columns]
+            for k, (r, v) in enumerate(cols):
+                if r.shape != v.shape:
+                    raise ValueError(f"panel column {k}: rows and vals differ in length")
+            colptr = np.zeros(len(cols) + 1, dtype=np.int64)
+            colptr[1:] = np.cumsum([len(r) for r, _ in cols])
+            rows = np.concatenate([r for r, _ in cols]) if colptr[-1] else np.zeros(0, np.int64)
+            vals = np.concatenate([v for _, v in cols]) if colptr[-1] else np.zeros(0)
+        self._chk(self.lib.mgmc_qoi_panel_set(self.handle, len(colptr) - 1, colptr.ctypes.data_as(P),
+                                              rows.ctypes.data_as(P), _dp(vals)))
+
+    def qoi_panel_eval(self, chain=0):
+        """z = (b_k^T x)_k of the current device state, nothing recorded: K values of one chain, or an
+        (nchains, K) array (chain=None)."""
+        K = self.qoi_panel_info()["K"]
+        out = np.empty((self.nchains, K))
+        self._chk(self.lib.mgmc_qoi_panel_eval(self.handle, _dp(out)))
+        return out if chain is None else out[int(chain)].copy()
+
+    def qoi_panel_record(self, stride: int = 1, window: int = 32, capacity: int = 4096):
+        """From now on every stride-th cycle (numbered 1, 2, ... from this call) records the panel of every chain
+        on the device: the series keeps the first `capacity` records; mean, co-moments and the autocovariance
+        over `window` lags (1 .. 256) keep counting.  On a sampler that already records with this window and
+        capacity: a reset with the new stride."""
+        self._chk(self.lib.mgmc_qoi_panel_record_enable(self.handle, int(stride), int(window), int(capacity)))
+        self._panel_capacity = int(capacity)
+
+    def qoi_panel_off(self):
+        """Free the record (the panel stays); the cycle is again the one of a sampler that never recorded."""
+        self._chk(self.lib.mgmc_qoi_panel_record_disable(self.handle))
+
+    def reset_qoi_panel(self):
+        """Zero the moments, the autocovariance, the record count and the cycle count of the thinning."""
+        self._chk(self.lib.mgmc_qoi_panel_record_reset(self.handle))
+
+    def qoi_panel_info(self) -> dict:
+        """{"K": columns (0: no panel), "enabled": bool, "stride", "window" (0 while disabled), "ncycles": cycles
+        seen, "nrecorded": cycles recorded since the enable / reset}"""
+        K, en, st, w = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        nc, nr = ctypes.c_uint64(), ctypes.c_uint64()
+        self._chk(self.lib.mgmc_qoi_panel_info(self.handle, ctypes.byref(K), ctypes.byref(en), ctypes.byref(st),
+                                               ctypes.byref(w), ctypes.byref(nc), ctypes.byref(nr)))
+        return {"K": K.value, "enabled": bool(en.value), "stride": st.value, "window": w.value,
+                "ncycles": nc.value, "nrecorded": nr.value}
+
+    def qoi_panel_series(self, chain: int = 0) -> np.ndarray:
+        """The records kept for one chain (the first `capacity` of them): an (n, K) array."""
+        info = self.qoi_panel_info()
+        if not info["enabled"]:  # (nothing is kept while disabled: the library refuses the call)
+            return np.empty((0, info["K"]))
+        n = min(info["nrecorded"], self._panel_capacity)
+        out = np.empty((n, info["K"]))
+        self._chk(self.lib.mgmc_qoi_panel_get_series(self.handle, int(chain), _dp(out), n))
+        return out
+
+    def qoi_panel_comoments(self, chain: int = 0):
+        """(n, mean[K], C[K, K]) of one chain as the device keeps them: C = sum (z - mean)(z - mean)^T."""
+        K = self.qoi_panel_info()["K"]
+        cnt = ctypes.c_double()
+        mean, C = np.empty(K), np.empty((K, K))
+        self._chk(self.lib.mgmc_qoi_panel_moments(self.handle, int(chain), ctypes.byref(cnt), _dp(mean), _dp(C)))
+        return cnt.value, mean, C
+
+    def qoi_panel_moments(self, chain=None):
+        """(n, mean, covariance): the covariance is the reference's n / (n - 1) (avg2 - avg avg^T)
+        (statistics.cc:41-45), that is C / (n - 1).  chain=None merges the chains in chain order with the matrix
+        form of Chan's formula (distributed.merge_panel_moments)."""
+        from .distributed import merge_panel_moments
+        if chain is None:
+            n, mean, C = merge_panel_moments([self.qoi_panel_comoments(c) for c in range(self.nchains)])
+        else:
+            n, mean, C = self.qoi_panel_comoments(chain)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return n, mean, C / (n - 1.0)
+
+    def qoi_panel_autocovariance(self, chain: int = 0):
+        """(S, nlags): S[k, j] = the running average of z_k(i) z_k(i - j) over the records (the diagonal of the
+        reference's S_j, statistics.cc:19-38), a (K, window) array of which the first nlags = min(window, records)
+        lags hold values.  The autocovariance is C_k(j) = S[k, j] - mean_k^2 (statistics.cc:54-62)."""
+        info = self.qoi_panel_info()
+        S = np.empty((info["K"], info["window"]))
+        nl = ctypes.c_int()
+        self._chk(self.lib.mgmc_qoi_panel_autocov(self.handle, int(chain), _dp(S), ctypes.byref(nl)))
+        return S, nl.value
+
+    def qoi_panel_tau_int(self, chain: int = 0) -> np.ndarray:
+        """tau_int of every column (the reference's unit directions, statistics.cc:65-80, :95-102) from the device's
+        S and mean: 1 + 2 sum_{j=1}^{L-1} (1 - j / L) C_k(j) / C_k(0), L the lags that hold values."""
+        S, L = self.qoi_panel_autocovariance(chain)
+        _, mean, _ = self.qoi_panel_comoments(chain)
+        return tau_int_from_autocov(S[:, :L] - (mean * mean)[:, None])
 
     def get_series(self, n: int, chain: int = 0) -> np.ndarray:
         """The QoI series of the last sample / sample_async call (waits for this handle's stream)."""
