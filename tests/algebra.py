@@ -27,7 +27,8 @@ colours of their reach-2 levels are the coordinates mod 3.
 
 Tolerance of A and B (componentwise, |lhs - rhs| <= C_TOL * EPS * s): s is the same expression with absolute
 values, every low-rank dot product weighted with the number of entries of its column (the gamma factor of a sum of
-that length; the blocked dots of a dense column otherwise reach 44 units).  The checks return max |lhs - rhs| /
+that length; the blocked dots of a dense column otherwise reach 44 units), plus the two terms of the sweep's
+Woodbury fix x' = y - B_bar (B^T y) (LevelAlgebra._lowrank_terms).  The checks return max |lhs - rhs| /
 (EPS * s); the tests assert it against C_TOL = 8 (measured: up to 4.2 for A, 6.8 for B; per case in the test files'
 docstrings)."""
 from __future__ import annotations
@@ -56,7 +57,9 @@ MATRIX_OPERATORS = {"fd": (mg.ShiftedLaplaceFDOperator, 0), "fem": (mg.ShiftedLa
 
 class Problem:
     """kind "fd" | "fem" | "stencil" (stencil: a tests/user_stencils.py name) on `shape` cells; kw over the SOR /
-    SSOR-coarse defaults; meas = (radius, number of measurements, measure_global) as in tests/test_gpu_lowrank.py.
+    SSOR-coarse defaults; meas = (radius, number of measurements, measure_global) as in tests/test_gpu_lowrank.py,
+    or the low-rank part itself: a measured.LowRankUpdate, or a callable lattice -> LowRankUpdate
+    (tests/lowrank_shapes.py).  The sampler of such a problem is the prior's with set_lowrank called on it.
 
     kind "matrix": an operator the library takes as a matrix (mgmc_create_csr).  pde "fd" | "fem" | "squared" with
     model "periodic" (PERIODIC) or "constant" (CONSTANT), or pde "dominant": the hand-made anisotropic matrix
@@ -71,6 +74,9 @@ class Problem:
         self.params = mg.MultigridParameters(**{"nlevel": 3, "smoother": "SOR", "coarse_solver": "SSOR", **kw})
         self.lat = mg.Lattice(*shape)
         self._faithful = None
+        self._lr = None
+        self._meas_is_lowrank = meas is not None and not isinstance(meas, tuple)
+        assert not self._meas_is_lowrank or kind == "fd"
 
     def _dominant(self):
         from tests.test_vardiag_host import dominant_matrix
@@ -89,7 +95,7 @@ class Problem:
         else:
             from tests import user_stencils as US
             op = mg.SparseMatrixOperator(self.lat, US.csr(self.shape, US.STENCILS[self.stencil]()))
-        if self.meas is not None:
+        if self.meas is not None and not self._meas_is_lowrank:
             from tests.test_gpu_lowrank import measured
             radius, nmeas, glob = self.meas
             assert self.kind == "fd"
@@ -97,6 +103,11 @@ class Problem:
         return op
 
     def lowrank(self):
+        if self._meas_is_lowrank:
+            if self._lr is None:
+                self._lr = self.meas(self.lat) if callable(self.meas) else self.meas
+                assert self._lr.n == self.lat.Nvertex
+            return self._lr
         return self.operator().get_B() if self.meas is not None else None
 
     def oracle(self, mode=O.MULTICOLOUR, seed=0, chain=0):
@@ -124,7 +135,10 @@ class Problem:
         return o
 
     def sampler(self, seed=0, chain=0, nchains=1):
-        return mg.MultigridMCSampler(self.operator(), seed, self.params, device=0, chain_id=chain, nchains=nchains)
+        s = mg.MultigridMCSampler(self.operator(), seed, self.params, device=0, chain_id=chain, nchains=nchains)
+        if self._meas_is_lowrank:
+            s.set_lowrank(self.lowrank())
+        return s
 
     def faithful(self):
         if self._faithful is None:
@@ -274,6 +288,8 @@ class LevelAlgebra:
         self.sd = np.sqrt(self.A.diagonal() * (2.0 - omega) / omega)
         self.xi_index, self.npairs = normal_index(self.shape)
         self.lr = None
+        self.bbar_term = True  # (False only to measure what the term of _lowrank_terms is worth)
+        self._bbar_cache = {}
 
     def _solve_split(self, direction, rhs):
         """M_dir^-1 rhs by substitution over the colour classes in sweep order (for the tolerance's scale only)."""
@@ -285,6 +301,26 @@ class LevelAlgebra:
             idx = np.flatnonzero(self.colour == c)
             u[idx] = (rhs[idx] - M[idx] @ u) / diag[idx]  # u is still zero on this and the later classes
         return u
+
+    def _bbar(self, direction):
+        """(|B_bar|, K) of a direction, from B, Sigma and the splitting assembled here (nothing from the library or
+        the oracle): Y = M_dir^-1 B column by column (_solve_split), K = Sigma + B^T Y, B_bar = Y K^-1 with K
+        inverted in extended precision (Gauss-Jordan with partial pivoting on long doubles)."""
+        if direction not in self._bbar_cache:
+            B, sig, _ = self.lr
+            m = len(sig)
+            Bd = B.toarray()
+            Y = np.stack([self._solve_split(direction, Bd[:, k]) for k in range(m)], axis=1).astype(np.longdouble)
+            K = np.diag(sig.astype(np.longdouble)) + Bd.T.astype(np.longdouble) @ Y
+            W = np.concatenate([K, np.eye(m, dtype=np.longdouble)], axis=1)
+            for c in range(m):
+                p = c + int(np.argmax(np.abs(W[c:, c])))
+                W[[c, p]] = W[[p, c]]
+                W[c] = W[c] / W[c, c]
+                rest = np.arange(m) != c
+                W[rest] = W[rest] - np.outer(W[rest, c], W[c])
+            self._bbar_cache[direction] = (np.abs(Y @ W[:, m:]).astype(np.float64), K)
+        return self._bbar_cache[direction]
 
     def _lowrank_terms(self, direction, xn, x):
         """(B Sigma^-1 B^T (x' - x), B Sigma^-1 B^T x, the low-rank part of s).  s takes the two products with
@@ -299,6 +335,14 @@ class LevelAlgebra:
         mag_d = np.abs(xn) + np.abs(x)
         u = 2.0 * np.abs(self._solve_split(direction, B @ ((B.T @ xn) / sig)))
         woodbury = self.absM[direction] @ u + aB @ (cnt * (aB.T @ u) / sig)
+        if self.bbar_term:
+            # ... and the rounding inside u = B_bar (B^T y) itself: an m-term fma chain against the stored B_bar =
+            # Y K^-1, gamma_m |B_bar| |B^T y| per component (B^T y = K Sigma^-1 B^T x'), which cancels heavily when
+            # the columns of Y are nearly collinear (64 measurements close together); carried by |M~| like the rest
+            abar, K = self._bbar(direction)
+            bty = np.abs((K @ ((B.T @ xn) / sig).astype(np.longdouble)).astype(np.float64))
+            v = len(sig) * (abar @ bty)
+            woodbury = woodbury + self.absM[direction] @ v + aB @ (cnt * (aB.T @ v) / sig)
         return (B @ ((B.T @ (xn - x)) / sig), B @ ((B.T @ x) / sig),
                 aB @ (cnt * (aB.T @ mag_d) / sig) + aB @ (cnt * (aB.T @ np.abs(x)) / sig) + woodbury)
 
@@ -345,18 +389,28 @@ class LevelAlgebra:
     # R: the residual + restriction onto the next level
     def residual_bound(self):
         """The bound of residual_ratio, derived: the row sum's rounding factor (its number of terms, the largest
-        row's), one for the subtraction from b, and 3^d for the restriction's sum (its weights are powers of two)."""
-        return float(np.diff(self.A.indptr).max() + 1 + 3 ** len(self.shape))
+        row's), one for the subtraction from b, and 3^d for the restriction's sum (its weights are powers of two).
+        A posterior level subtracts B Sigma^-1 B^T x as well: per row one term per stored B_ik (the fullest row's
+        count), each a product and a quotient (2), on a dot whose own factor -- its column's length -- is in s."""
+        bound = float(np.diff(self.A.indptr).max() + 1 + 3 ** len(self.shape))
+        if self.lr is not None:
+            bound += float(np.diff(self.lr[0].tocsr().indptr).max() + 2)
+        return bound
 
     def residual_ratio(self, be, b, x):
-        """R: residual_restrict(level, b, x) = P^T (b - A_l x) componentwise, P from its definition; the ratio
-        |got - ref| / (EPS P^T (|b| + |A_l| |x|))."""
+        """R: residual_restrict(level, b, x) = P^T (b - Q_l x) componentwise, P from its definition, Q_l = A_l (+
+        B_l Sigma^-1 B_l^T on a posterior level); the ratio |got - ref| / (EPS P^T (|b| + |A_l| |x| + |B_l| Sigma^-1
+        (column lengths o |B_l|^T |x|)))."""
         P = interpolation(self.shape)
         got = be.residual_restrict(self.level, b, x)
         assert got.shape == (P.shape[1],) and np.all(np.isfinite(got))
-        ref = P.T @ (b - self.A @ x)
-        s = P.T @ (np.abs(b) + self.absA @ np.abs(x))
-        return float(np.max(np.abs(got - ref) / (EPS * s)))
+        r = b - self.A @ x
+        mag = np.abs(b) + self.absA @ np.abs(x)
+        if self.lr is not None:
+            B, sig, cnt = self.lr
+            r = r - B @ ((B.T @ x) / sig)
+            mag = mag + abs(B) @ (cnt * (abs(B).T @ np.abs(x)) / sig)
+        return float(np.max(np.abs(got - P.T @ r) / (EPS * (P.T @ mag))))
 
 
 def check_residuals(prob, be, rng, algebras):

@@ -9,10 +9,11 @@ shapes that reach its fast kernels.
 
 Largest ratios |lhs - rhs| / (EPS s) measured on the oracle (bound C_TOL = 8), per case: A / B / A and B at once:
     3d_24x20x12_w11 1.88 / 6.84 / 2.43    2d_34x18_w08 2.07 / 2.36 / 1.84    3d16 2.40 / 4.83 / 2.81
-    2d32_point_global 0.57 / 0.85 / 0.78  3d32_ball_global 0.08 / 0.21 / 0.12
+    2d32_point_global 0.45 / 0.68 / 0.34  3d32_ball_global 0.07 / 0.15 / 0.11
     fem2d32 2.09 / 3.57 / 2.25            c27_24x20x12 4.17 / 4.45 / 3.54
 (B of 2d32_point_global is 75.7 at the three measured vertices without the Woodbury term of s,
-algebra.LevelAlgebra._lowrank_terms.)  Whole cycles: CYCLE_REFERENCE below.
+algebra.LevelAlgebra._lowrank_terms; the two low-rank cases were 0.57 / 0.85 / 0.78 and 0.08 / 0.21 / 0.12 before s
+took the rounding of u = B_bar (B^T y) as well, tests/test_lowrank_shapes_host.py.)  Whole cycles: CYCLE_REFERENCE below.
 Matrix-built problems (Oracle.csr on the oracle's own assembly; the device takes them through mgmc_create_csr):
     m_fd_periodic_24x20x12_w11 2.09 / 4.32 / 2.59   m_fd_periodic_34x18_w08 1.53 / 3.79 / 2.18
     m_fem_periodic_16 2.52 / 5.31 / 2.77            m_squared_32 2.39 / 4.32 / 2.61 (9 colours on all 3 levels)
